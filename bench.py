@@ -8,11 +8,14 @@ FFHQ-shaped uint8 pools that are resident in HBM before the timed region (BASELI
 images/sec = global batch / iteration time, the reference's own instrument
 (confignet_first_stage.py:605-625).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 N > 1: one process per GPU, same per-GPU batch (weak scaling), gradient arenas all-reduced with RCCL.
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline (images/sec,
+ms_per_step); --full adds everything else this command measures: per-step-function times, the roofline pass, the
+CPU baseline with its loss-parity check and the `secondary` block.  --dump-outputs DIR writes the losses that one
+more step of the timed path returns from the seeded starting state (dump_outputs).
 """
 import argparse
 import json
@@ -51,6 +54,12 @@ def main():
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
                     help="f32: the reference's arithmetic (BASELINE.json configs[1], the headline).  bf16: configs[2]'s compute type "
                          "(bf16 activations / filter copies on bf16 MFMA, fp32 accumulate, fp32 master weights) -- a separate line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the per-step-function times, the roofline pass, the CPU baseline with "
+                         "its loss parity and the `secondary` block (a plain run does the timed loop only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, restore the seeded starting state, run one more step of the timed path (same "
+                         "graphs, same dispatch) and write the loss scalars it returns as DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
     import torch
@@ -82,6 +91,7 @@ def main():
         torch.cuda.set_device(0)
 
     model, real_set, synth_set, d_opt, g_opt, cfg = setup(args.batch, args.res, args.pool, rank)
+    start = starting_state(model) if args.dump_outputs else None     # (seeded weights + batch stream, before any step)
 
     def sync():
         torch.cuda.synchronize()
@@ -114,10 +124,50 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     finite = all(np.isfinite(float(l["loss_sum"].detach())) for l in losses)
+    if args.dump_outputs:
+        # every rank runs the step (its all-reduces need them all); rank 0 writes
+        out_losses = step_from(start, model, real_set, synth_set, d_opt, g_opt)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, out_losses)
 
-    # Loss parity of THE DISPATCH JUST TIMED against the CPU oracle at this very size (rank 0, N = 1): one more iteration of the
-    # same loop (replayed graphs, its real halves already in flight from the previous iteration) on fresh Adam moments; its
-    # weights and batches go to the oracle subprocess of the cpu_baseline leg, which runs the same iteration first.
+    def slowest(seconds):
+        t = torch.tensor([seconds], dtype=torch.float64, device="cuda")
+        if world > 1:
+            parallel.all_reduce_max(t)
+        return float(t.item())
+
+    def headline(elapsed):
+        ms_per_step = 1e3 * elapsed / args.steps
+        return {
+            "metric": "train-step images/sec at 256x256 (G+D fwd+bwd)",
+            "value": round(args.batch * world / (elapsed / args.steps), 3), "unit": "images/sec", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": args.dtype,
+            "data": "synthetic",
+            "config": {"workload": "ConfigNet second-stage iteration (D + synth-D + latent-D + G + EMA), %dx%d, "
+                                   "batch %d per GPU, %s, Keras-Adam" % (args.res, args.res, args.batch,
+                                                                          "fp32" if args.dtype == "f32" else "bf16 compute / fp32 master weights"),
+                       "global_batch": args.batch * world, "resolution": args.res, "latent_dim": cfg_latent(model),
+                       "parallelism": "dp%d" % world, "losses_finite": bool(finite),
+                       "pipelining": ("steady state across iterations: the real half of the discriminator steps of iteration k+1 runs under "
+                                      "the generator tail of iteration k, so the timed window holds the halves of iterations 2..K+1 instead "
+                                      "of 1..K -- K iterations' worth of every kernel either way; CN_NO_D_OVERLAP=1 times the unpipelined loop"
+                                      if model.overlap_discriminators else "none (every iteration starts after the previous one has finished)"),
+                       "dispatch": ("eager, one stream" if args.serial else "eager" if args.no_graphs else
+                                    "hip-graph replay per step function, D-type steps concurrent, G step forked over 2 streams" +
+                                    (", real half of the next iteration's discriminator steps" + (" and the generator step's ground-truth VGG passes" if getattr(model, "_targets_ahead", None) is not None else "") + " under the generator tail" if model.overlap_discriminators else "") +
+                                    ("" if not parallel.active() else " (fwd+bwd), eager %s all-reduce + Adam" %
+                                     ("RCCL" if dist.get_backend() == "nccl" else "gloo (through the host: ranks share a device)")))},
+        }
+
+    def emit(out):
+        if not finite:
+            # a timed loop whose losses went non-finite is not a measurement of the workload (round 4: such runs were also faster)
+            out["invalid"] = "non-finite losses in the timed loop"
+            print("bench.py: NON-FINITE LOSSES in the timed loop -- this line is not a valid measurement", file=sys.stderr, flush=True)
+        print(json.dumps(out), flush=True)
+
     if args.timing_only:
         if rank == 0:
             print(json.dumps({"value": round(args.batch * world / (elapsed / args.steps), 3), "unit": "images/sec", "dtype": args.dtype,
@@ -127,6 +177,19 @@ def main():
             dist.barrier()
             dist.destroy_process_group()
         return
+    if not args.full:
+        elapsed = slowest(elapsed)
+        if rank == 0:
+            emit(headline(elapsed))
+        if dist.is_initialized():
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # --full from here on.
+    # Loss parity of THE DISPATCH JUST TIMED against the CPU oracle at this very size (rank 0, N = 1): one more iteration of the
+    # same loop (replayed graphs, its real halves already in flight from the previous iteration) on fresh Adam moments; its
+    # weights and batches go to the oracle subprocess of the cpu_baseline leg, which runs the same iteration first.
     parity_state = None
     if world == 1 and not args.no_cpu_baseline and not args.no_parity:
         parity_state = dump_parity_state(model, real_set, synth_set, d_opt, g_opt)
@@ -176,36 +239,14 @@ def main():
                  for k, v in sorted(families.items(), key=lambda kv: -kv[1]["ms"])}
     alg_bytes_per_step = sum(v["algorithmic_mb"] for v in families.values()) * 1e6 / nst
 
-    t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
-    if world > 1:
-        parallel.all_reduce_max(t)
-    elapsed = float(t.item())
+    elapsed = slowest(elapsed)
 
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
-        value = args.batch * world / (elapsed / args.steps)
         achieved = kernel_flops / (kernel_ms * 1e-3) / 1e12 if kernel_ms > 0 else 0.0
         peak = FP32_MFMA_PEAK_TFLOPS if args.dtype == "f32" else BF16_MFMA_PEAK_TFLOPS
-        out = {
-            "metric": "train-step images/sec at 256x256 (G+D fwd+bwd)",
-            "value": round(value, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": args.dtype,
-            "data": "synthetic",
-            "config": {"workload": "ConfigNet second-stage iteration (D + synth-D + latent-D + G + EMA), %dx%d, "
-                                   "batch %d per GPU, %s, Keras-Adam" % (args.res, args.res, args.batch,
-                                                                          "fp32" if args.dtype == "f32" else "bf16 compute / fp32 master weights"),
-                       "global_batch": args.batch * world, "resolution": args.res, "latent_dim": cfg_latent(model),
-                       "parallelism": "dp%d" % world, "losses_finite": bool(finite),
-                       "pipelining": ("steady state across iterations: the real half of the discriminator steps of iteration k+1 runs under "
-                                      "the generator tail of iteration k, so the timed window holds the halves of iterations 2..K+1 instead "
-                                      "of 1..K -- K iterations' worth of every kernel either way; CN_NO_D_OVERLAP=1 times the unpipelined loop"
-                                      if model.overlap_discriminators else "none (every iteration starts after the previous one has finished)"),
-                       "dispatch": ("eager, one stream" if args.serial else "eager" if args.no_graphs else
-                                    "hip-graph replay per step function, D-type steps concurrent, G step forked over 2 streams" +
-                                    (", real half of the next iteration's discriminator steps" + (" and the generator step's ground-truth VGG passes" if getattr(model, "_targets_ahead", None) is not None else "") + " under the generator tail" if model.overlap_discriminators else "") +
-                                    ("" if not parallel.active() else " (fwd+bwd), eager %s all-reduce + Adam" %
-                                     ("RCCL" if dist.get_backend() == "nccl" else "gloo (through the host: ranks share a device)")))},
+        out = headline(elapsed)
+        out.update({
             "step_functions_ms": step_ms,
             "roofline": {"bound": "mfma", "achieved": round(achieved, 3), "peak": peak, "unit": "TFLOP/s",
                          "frac": round(achieved / peak, 4), "traffic": pmc_traffic(args.dtype),
@@ -254,7 +295,7 @@ def main():
             "torch_kernel_time_share": torch_kernel_share(),
             # kernel launches of one iteration, from the committed rocprofv3 trace of `bench.py --serial` (recorded, like the PMC fields)
             "launches_per_iteration": _recorded("round6_torch_share.json", "launches_per_iteration"),
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"], ref_losses = cpu_baseline(args, parity_state["path"] if parity_state else None)
             if parity_state is not None:
@@ -265,11 +306,7 @@ def main():
                     pass
         if world == 1 and not args.no_secondary and not args.no_cpu_baseline and args.dtype == "f32":     # (the full line only: auxiliary / traced runs pass --no-cpu-baseline)
             out["secondary"] = secondary(args)
-        if not finite:
-            # a timed loop whose losses went non-finite is not a measurement of the workload (round 4: such runs were also faster)
-            out["invalid"] = "non-finite losses in the timed loop"
-            print("bench.py: NON-FINITE LOSSES in the timed loop -- this line is not a valid measurement", file=sys.stderr, flush=True)
-        print(json.dumps(out), flush=True)
+        emit(out)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()
@@ -399,6 +436,58 @@ PARITY_NETS = ("generator", "generator_smoothed", "discriminator", "synth_discri
                "latent_regressor", "synthetic_encoder", "real_encoder")
 
 
+def named_networks(model):
+    return dict(zip(PARITY_NETS, (model.generator, model.generator_smoothed, model.discriminator, model.synth_discriminator,
+                                  model.latent_discriminator, model.latent_regressor, model.synthetic_encoder, model.encoder)))
+
+
+def fresh_optimizers(*opts):
+    """Adam moments and step counters back to a new optimizer's (zeros, t = 0), in place: the step graphs keep their buffers."""
+    for o in opts:
+        o.iterations = 0
+        for mom, var in o._state.values():
+            mom.zero_()
+            var.zero_()
+
+
+def starting_state(model):
+    """The state right after setup(): every network's weights (seeded) and the np.random stream the steps draw batches from."""
+    return {name: net.get_weights() for name, net in named_networks(model).items()}, np.random.get_state()
+
+
+def step_from(start, model, real_set, synth_set, d_opt, g_opt):
+    """ONE more iteration of the timed path -- same model, same captured graphs, same dispatch -- from the starting state:
+    weights restored, fresh Adam moments (as at the first step), the batch stream rewound.  Restoring bumps every network's
+    epoch, so the halves that the last timed iteration pre-replayed under its generator tail are not consumed but redone
+    from their host halves (ConfigNetFirstStage._image_discriminator_step).  Its inputs are therefore the same in every run,
+    whatever the timed iterations before it did: in the default dispatch fp32 atomics and the forked generator step make
+    iterations of a GAN drift apart (Keras-Adam moves each weight by about lr * sign(g)), so the losses of the K-th timed
+    iteration are not reproducible from run to run -- those of one iteration from the seeded start are, up to rounding
+    (about 1e-4 relative at most between runs, as far as the fixed-order reductions of CN_DETERMINISTIC=1 land from them).
+    Returns the four loss dicts (host floats)."""
+    import torch
+    torch.cuda.synchronize()
+    weights, rng = start
+    for name, net in named_networks(model).items():
+        net.set_weights(weights[name])
+    fresh_optimizers(d_opt, g_opt)
+    np.random.set_state(rng)
+    out = model.training_iteration(real_set, synth_set, d_opt, g_opt)
+    torch.cuda.synchronize()
+    return [{k: float(v.detach()) if hasattr(v, "detach") else float(v) for k, v in d.items()} for d in out]
+
+
+def dump_outputs(path, losses):
+    """step_from()'s four loss dicts, one float32 scalar per file (the precision they are computed in):
+    DIR/loss_<step>__<name>.npy, step in d / synth_d / latent_d / g -- what a caller of the training iteration receives, for
+    comparing two builds output for output."""
+    import re
+    os.makedirs(path, exist_ok=True)
+    for step, d in zip(("d", "synth_d", "latent_d", "g"), losses):
+        for k, v in d.items():
+            np.save(os.path.join(path, "loss_%s__%s.npy" % (step, re.sub(r"[^A-Za-z0-9_.-]", "_", k))), np.array(v, np.float32))
+
+
 def dump_parity_state(model, real_set, synth_set, d_opt, g_opt, path=None):
     """Runs ONE MORE iteration in the dispatch the caller has set up and writes what the CPU oracle needs to run the same
     iteration (oracle/cpu_baseline.py:load_state): every network's weights before it, the batches (uint8 images gathered ON
@@ -409,8 +498,7 @@ def dump_parity_state(model, real_set, synth_set, d_opt, g_opt, path=None):
     import tempfile
 
     import torch
-    nets = dict(zip(PARITY_NETS, (model.generator, model.generator_smoothed, model.discriminator, model.synth_discriminator,
-                                  model.latent_discriminator, model.latent_regressor, model.synthetic_encoder, model.encoder)))
+    nets = named_networks(model)
     model._bufs.log = {}
     model.training_iteration(real_set, synth_set, d_opt, g_opt)           # (its tail stages the discriminator batches of the next one)
     torch.cuda.synchronize()
@@ -419,11 +507,7 @@ def dump_parity_state(model, real_set, synth_set, d_opt, g_opt, path=None):
     # (the latent-discriminator and generator steps' host halves move with them when the generator step's ground-truth VGG
     # passes are replayed ahead: ConfigNet._prelaunch_generator_targets)
     ahead = (("d/", "sd/") if pipelined else ()) + (("ld/", "g/") if (pipelined and "g" in model._prestaged) else ())
-    for o in (d_opt, g_opt):
-        o.iterations = 0
-        for mom, var in o._state.values():
-            mom.zero_()
-            var.zero_()
+    fresh_optimizers(d_opt, g_opt)
     z = {}
     for name, net in nets.items():
         ws = net.get_weights()

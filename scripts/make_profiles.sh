@@ -12,18 +12,18 @@ cd /tmp && export TMPDIR=/tmp
 PY="python"
 if [ "$ONLY" = all ]; then
 # 1. the bench lines (default flags), fp32 and bf16
-timeout 900 $PY $R/bench.py > $O/${TAG}_bench.json 2> $O/bench.err
-timeout 300 $PY $R/bench.py --dtype bf16 --no-cpu-baseline > $O/${TAG}_bench_bf16.json 2>> $O/bench.err
+timeout 900 $PY $R/bench.py --full > $O/${TAG}_bench.json 2> $O/bench.err
+timeout 300 $PY $R/bench.py --full --dtype bf16 --no-cpu-baseline > $O/${TAG}_bench_bf16.json 2>> $O/bench.err
 # 1b. 400-step soaks of the same two commands (a 20-step mean is 0.8 s of work)
-timeout 600 $PY $R/bench.py --steps 400 --no-cpu-baseline > $O/${TAG}_bench_400_steps.json 2>> $O/bench.err
-timeout 600 $PY $R/bench.py --steps 400 --dtype bf16 --no-cpu-baseline > $O/${TAG}_bench_bf16_400_steps.json 2>> $O/bench.err
+timeout 600 $PY $R/bench.py --full --steps 400 --no-cpu-baseline > $O/${TAG}_bench_400_steps.json 2>> $O/bench.err
+timeout 600 $PY $R/bench.py --full --steps 400 --dtype bf16 --no-cpu-baseline > $O/${TAG}_bench_bf16_400_steps.json 2>> $O/bench.err
 timeout 600 $PY $R/bench.py --steps 2000 --timing-only > $O/${TAG}_bench_2000_steps.json 2>> $O/bench.err
 timeout 600 $PY $R/bench.py --steps 2000 --timing-only --dtype bf16 > $O/${TAG}_bench_bf16_2000_steps.json 2>> $O/bench.err
 # 2. kernel traces: the default (concurrent graphs) command and the serial one whose averages the roofline object quotes
 rm -rf /tmp/kt1 /tmp/kt2
-timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/kt1 -- $PY $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/${TAG}_bench_under_rocprof.json 2>/dev/null
+timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/kt1 -- $PY $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $O/${TAG}_bench_under_rocprof.json 2>/dev/null
 $PY $R/scripts/prof_summary.py $(ls /tmp/kt1/*/*.db | head -1) > $O/${TAG}_bench_kernel_trace.txt
-timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/kt2 -- $PY $R/bench.py --serial --steps 10 --warmup 3 --no-cpu-baseline > $O/${TAG}_bench_serial_under_rocprof.json 2>/dev/null
+timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/kt2 -- $PY $R/bench.py --full --serial --steps 10 --warmup 3 --no-cpu-baseline > $O/${TAG}_bench_serial_under_rocprof.json 2>/dev/null
 $PY $R/scripts/prof_summary.py $(ls /tmp/kt2/*/*.db | head -1) > $O/${TAG}_bench_serial_kernel_trace.txt
 $PY $R/scripts/torch_share.py /tmp/kt2 $O/${TAG}_torch_share.json > /dev/null
 # 2b. the generator step alone (eager, one stream: the kernel composition of the iteration's backbone) and the device timeline
@@ -40,13 +40,13 @@ pmc_pass() {   # pmc_pass <out dir> <stdout file> <bench flags...> -- <counters.
   local flags=(); while [ "$1" != "--" ]; do flags+=("$1"); shift; done; shift
   for try in 1 2 3; do
     rm -rf $out
-    timeout 600 rocprofv3 --kernel-trace --pmc "$@" -d $out -- $PY $R/bench.py "${flags[@]}" > $line 2>/dev/null
+    timeout 600 rocprofv3 --kernel-trace --pmc "$@" -d $out -- $PY $R/bench.py --full "${flags[@]}" > $line 2>/dev/null
     if ls $out/*/*.db > /dev/null 2>&1; then return 0; fi
     echo "pmc pass $out: no database (try $try)" >> $O/bench.err
   done
   return 1
 }
-CMD="bench.py --steps 2 --warmup 1 --no-cpu-baseline --serial"
+CMD="bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --serial"
 pmc_pass /tmp/pf /tmp/pf_line.json --steps 2 --warmup 1 --no-cpu-baseline --serial -- FETCH_SIZE
 pmc_pass /tmp/pw /dev/null --steps 2 --warmup 1 --no-cpu-baseline --serial -- WRITE_SIZE
 $PY $R/scripts/pmc_traffic_json.py /tmp/pf /tmp/pw $O/${TAG}_pmc_traffic.json "python $CMD" > /dev/null
@@ -56,7 +56,7 @@ $PY $R/scripts/pmc_mfma.py /tmp/pm $O/${TAG}_pmc_mfma.json > $O/${TAG}_pmc_mfma.
 # 3a. one table per kernel: launches | us | MFMA-busy | t_mfma | t_rest | traffic ratio (the overlap claim, checkable in one file)
 $PY $R/scripts/overlap_table.py /tmp/pm $O/${TAG}_pmc_traffic_by_kernel.json $O/${TAG}_overlap_table.txt > /dev/null
 # 3b. the same counters for the bf16 path (configs[2]'s dtype)
-CMDB="bench.py --steps 2 --warmup 1 --no-cpu-baseline --serial --dtype bf16"
+CMDB="bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --serial --dtype bf16"
 pmc_pass /tmp/pfb /tmp/pfb_line.json --steps 2 --warmup 1 --no-cpu-baseline --serial --dtype bf16 -- FETCH_SIZE
 pmc_pass /tmp/pwb /dev/null --steps 2 --warmup 1 --no-cpu-baseline --serial --dtype bf16 -- WRITE_SIZE
 $PY $R/scripts/pmc_traffic_json.py /tmp/pfb /tmp/pwb $O/${TAG}_pmc_traffic_bf16.json "python $CMDB" > /dev/null

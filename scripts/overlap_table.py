@@ -1,7 +1,7 @@
 """profiles/roundN_overlap_table.txt: one row per kernel of the convolution class -- launches, average duration, MFMA-busy fraction,
 the time its matrix pipes were busy (t_mfma) and the rest (t_rest = duration - t_mfma: operand delivery, ramp / tail, barriers,
 epilogue that did NOT overlap the MFMAs), and the measured / algorithmic traffic ratio of its family where the byte model has one.
-Inputs: the rocprofv3 PMC pass with SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE (+ --kernel-trace) over `bench.py --serial`, and the
+Inputs: the rocprofv3 PMC pass with SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE (+ --kernel-trace) over `bench.py --full --serial`, and the
 by-kernel traffic json of scripts/pmc_traffic_by_kernel.py.
 usage: overlap_table.py <mfma_pass_dir> <traffic_by_kernel.json> <out.txt>"""
 import glob, json, os, sqlite3, sys
@@ -62,7 +62,7 @@ for k, c in acc.items():
     us = dur[k] / max(ndur[k], 1) / 1e3 if ndur[k] else gui / 8 / calls[k] / 2.4e3      # (no trace table: elapsed cycles at 2.4 GHz)
     rows.append((us * calls[k], k, calls[k], us, frac, us * frac, us * (1 - frac), (traffic.get(family(k)) or {}).get("ratio")))
 with open(sys.argv[3], "w") as fp:
-    fp.write("# kernels_hash %s; rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CU_CYCLES -- python bench.py --serial --steps 2 --warmup 1\n" % kernels_hash())
+    fp.write("# kernels_hash %s; rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CU_CYCLES -- python bench.py --full --serial --steps 2 --warmup 1\n" % kernels_hash())
     fp.write("# t_mfma = duration x MFMA-busy; t_rest = duration - t_mfma (what did not overlap the matrix pipe); traffic = measured / algorithmic bytes of the kernel's family\n")
     fp.write("%-62s %8s %9s %9s %9s %9s %8s %8s\n" % ("kernel", "launches", "us", "MFMA-busy", "t_mfma us", "t_rest us", "traffic", "share"))
     tot = sum(r[0] for r in rows)

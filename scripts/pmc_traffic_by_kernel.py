@@ -1,5 +1,5 @@
 """profiles/roundN_pmc_traffic_by_kernel.txt: measured HBM-side bytes per launch of every kernel of the convolution class
-(rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes over `bench.py --serial --steps K`) next to the ALGORITHMIC
+(rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes over `bench.py --full --serial --steps K`) next to the ALGORITHMIC
 bytes per launch of the same kernels (every operand read once, the result written once: cn_prof_collect_by_family, printed by
 the bench line of the same command as roofline.by_kernel).
 usage: pmc_traffic_by_kernel.py <fetch_dir> <write_dir> <bench_line.json> <out.txt> [<out.json>]"""
@@ -66,7 +66,7 @@ for f in sorted(set(fetch) | set(write), key=lambda k: -(fetch[k][1] * 2 + write
         tot_m += meas * nf
         tot_a += alg * 1e6 * nf
 with open(sys.argv[4], "w") as fp:
-    fp.write("# kernels_hash %s; command: %s\n" % (kernels_hash(), line.get("command", "python bench.py --serial")))
+    fp.write("# kernels_hash %s; command: %s\n" % (kernels_hash(), line.get("command", "python bench.py --full --serial")))
     fp.write("# HBM-side bytes per launch: FETCH_SIZE doubled (MI355X_MICROARCH.md: gfx950 reports half of wide coalesced reads;\n"
              "# scalar / narrow accesses are not under-reported, so the doubled figure is an UPPER bound for kernels with such\n"
              "# loads) + WRITE_SIZE (uncalibrated); algorithmic = x, w read once + y written once (cn_prof_collect_by_family).\n"
