@@ -40,6 +40,7 @@ class CnConvGeom(ctypes.Structure):
 
 
 CN_F32, CN_BF16 = 0, 1          # dtype codes of activation tensors (include/confignet_hip.h)
+CN_U8 = 2                       # uint8 pixels (cn_image_preprocess input)
 CN_EUNSUPPORTED = -3
 
 
@@ -128,6 +129,8 @@ SIGNATURES = {
     "cn_maxpool_fwd": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "cn_maxpool_bwd": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "cn_avgpool3_same": [_p, _p, _i, _i, _i, _i, _i, _p],
+    "cn_dwconv3x3_fwd": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p],
+    "cn_image_preprocess": [_p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _f, _p],
     "cn_chan_affine3_fwd": [_p, _p, _z, ctypes.POINTER(_i), _f, ctypes.POINTER(_f), _p],
     "cn_chan_affine3_bwd": [_p, _p, _z, ctypes.POINTER(_i), _f, _p],
     "cn_gan_loss_fwd": [_p, _p, _i, _f, _p],

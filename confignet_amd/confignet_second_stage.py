@@ -33,6 +33,7 @@ class ConfigNet(ConfigNetFirstStage):
         self.config["model_type"] = "ConfigNet"
         self.encoder = None
         self.generator_fine_tuned = None
+        self.controllability_metrics = None
         self.perceptual_loss_face_reco = PerceptualLoss(self.config["output_shape"], model_type="VGGFace")
         if initialize:
             self.initialize_network()
@@ -401,8 +402,17 @@ class ConfigNet(ConfigNetFirstStage):
 
     def setup_training(self, log_dir, synth_training_set, n_samples_for_metrics, attribute_classifier=None,
                        real_training_set=None, validation_set=None):
-        """confignet_second_stage.py:255-266 (ControllabilityMetrics: out of scope)."""
+        """confignet_second_stage.py:255-266.  attribute_classifier: a CelebaAttributeClassifier or the path of its .json
+        enables the controllability metrics (blendshape names from synth_training_set, the beard-style map from
+        config["beard_style_map_path"]); None or "none" leaves them off."""
         super(ConfigNet, self).setup_training(log_dir, synth_training_set, n_samples_for_metrics, real_training_set)
+        self.controllability_metrics = None
+        if attribute_classifier is not None and not (isinstance(attribute_classifier, str) and attribute_classifier.lower() == "none"):
+            from .metrics import ControllabilityMetrics
+            labels = getattr(synth_training_set, "metadata_input_labels", None) or {}
+            self.controllability_metrics = ControllabilityMetrics(self, attribute_classifier,
+                                                                  blendshape_names=labels.get("blendshape_values"),
+                                                                  beard_style_map=self.config.get("beard_style_map_path"))
         if validation_set is None:
             validation_set = real_training_set if real_training_set is not None else synth_training_set
         imgs = validation_set.imgs
@@ -418,9 +428,12 @@ class ConfigNet(ConfigNetFirstStage):
         return sel.astype(np.float32) / 127.5 - 1.0
 
     def calculate_metrics(self, output_dir, aml_run=None):
-        """confignet_second_stage.py:220-253: FID/KID (first stage) + the perceptual reconstruction metric of the metric
-        images through encoder -> smoothed generator; the controllability metrics are out of scope."""
+        """confignet_second_stage.py:220-253: FID/KID (first stage), the controllability metrics (when an attribute classifier
+        was given) and the perceptual reconstruction metric of the metric images through encoder -> smoothed generator."""
         super(ConfigNet, self).calculate_metrics(output_dir, aml_run)
+        if self.controllability_metrics is not None:
+            self.controllability_metrics.update_and_log_metrics(self._generator_input_for_metrics["input_images"], self.metrics,
+                                                                output_dir, aml_run)
         inp = self._generator_input_for_metrics["input_images"]
         latents, rotations = self.encode_images(inp)
         generated = self.generator_smoothed.predict(self.generator_smoothed.build_input_dict(latents, rotations))

@@ -83,8 +83,12 @@ __device__ __forceinline__ float cn_apply_act(float v, int act, float slope) {
         case CN_ACT_LRELU: return v > 0.f ? v : v * slope;
         case CN_ACT_RELU: return v > 0.f ? v : 0.f;
         case CN_ACT_TANH: return tanhf(v);
-        default: return v;
+        default: break;
     }
+    // the classifier's codes (CN_ACT_RELU6, CN_ACT_SIGMOID) behind the original three: the dispatch of those stays as it was
+    if (act == CN_ACT_RELU6) return fminf(fmaxf(v, 0.f), 6.f);
+    if (act == CN_ACT_SIGMOID) return __fdividef(1.f, 1.f + __expf(-v));        // (native exp / rcp: rel. error ~1e-6)
+    return v;
 }
 
 static inline int cn_cdiv(long a, long b) { return (int)((a + b - 1) / b); }

@@ -137,6 +137,15 @@ class NeuralRendererDataset:
         finally:
             self.imgs = imgs
 
+    def get_attribute_values(self, sample_idxs, attribute_names):
+        """neural_renderer_dataset.py:312-321: (len(sample_idxs), len(attribute_names)) array of the per-image CelebA attributes."""
+        assert self.attributes is not None
+        attribute_values = []
+        for idx in sample_idxs:
+            sample_attributes = self.attributes[idx]
+            attribute_values.append([sample_attributes[name] for name in attribute_names])
+        return np.array(attribute_values)
+
     def process_metadata(self, config, update_config=False):
         """neural_renderer_dataset.py:150-228: per face-model input named in config["facemodel_inputs"] (a key, or a
         ':'-separated path into the per-image render metadata): strings -> one-hot over the sorted unique values

@@ -8,9 +8,9 @@ import threading
 
 import torch
 
-from ._lib import CN_BF16, CN_EUNSUPPORTED, CN_F32, CnConvGeom, CnDepthJob, CnGanJob, CnRowsJob, CnSumJob, check, lib
+from ._lib import CN_BF16, CN_EUNSUPPORTED, CN_F32, CN_U8, CnConvGeom, CnDepthJob, CnGanJob, CnRowsJob, CnSumJob, check, lib
 
-ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH = 0, 1, 2, 3
+ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH, ACT_RELU6, ACT_SIGMOID = 0, 1, 2, 3, 4, 5
 
 # Storage type of ACTIVATION tensors (channels-last tensors with more than 4 channels).  fp32 is the reference's arithmetic
 # (BASELINE.json configs[1]); bf16 is configs[2]: bf16 activations and bf16 filter copies on v_mfma_f32_32x32x16_bf16 with
@@ -1441,6 +1441,37 @@ def avgpool3_same(x):
     x = _c(x)
     y = torch.empty_like(x)
     check(lib.cn_avgpool3_same(_ptr(x), _ptr(y), n, h, w, c, _dt(x), _stream()), "cn_avgpool3_same")
+    return y
+
+
+def dwconv3x3_fwd(x, w, bias, stride, act=ACT_NONE, slope=0.0):
+    """keras DepthwiseConv2D(3, strides=stride, depth_multiplier=1) on an NHWC fp32 tensor, TF "same" padding (the
+    ZeroPadding2D(correct_pad) + VALID pair of MobileNetV2's stride-2 layers pads the same), + per-channel bias, + activation:
+    (n, h, w, c) -> (n, ceil(h / stride), ceil(w / stride), c).  w: the Keras kernel (3, 3, c, 1)."""
+    x = _c(f32(x))
+    n, h, wd, c = x.shape
+    assert tuple(w.shape) in ((3, 3, c, 1), (3, 3, c)), "depthwise kernel (3, 3, %d, 1) expected, got %s" % (c, tuple(w.shape))
+    assert bias is None or tuple(bias.shape) == (c,)
+    y = torch.empty((n, -(-h // stride), -(-wd // stride), c), device=x.device, dtype=torch.float32)
+    check(lib.cn_dwconv3x3_fwd(_ptr(x), _fptr(_c(w)), _fptr(None if bias is None else _c(bias)), _ptr(y), n, h, wd, c, stride, act, slope,
+                               _stream()), "cn_dwconv3x3_fwd")
+    return y
+
+
+def image_preprocess(imgs, out_hw, from_signed=False):
+    """A batch of images (n, h, w, c), uint8 or float32 in pixel units [0, 255], -> the MobileNetV2 input (n, out_h, out_w, c)
+    fp32 in one launch: bilinear resampling with half-pixel centres and edge clamping (cv2.resize INTER_LINEAR) when the size
+    differs, then keras mobilenet_v2.preprocess_input (x / 127.5 - 1).  from_signed: float input in [-1, 1], mapped
+    (x + 1) * 127.5 first.  uint8 input is interpolated in float: cv2's 11-bit fixed-point uint8 path is not reproduced, so
+    results can differ from a cv2.resize of the same uint8 image by about one grey level before the scaling."""
+    imgs = _c(imgs)
+    assert imgs.dtype in (torch.uint8, torch.float32), imgs.dtype
+    n, h, wd, c = imgs.shape
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    y = torch.empty((n, oh, ow, c), device=imgs.device, dtype=torch.float32)
+    mul, add = (127.5, 127.5) if from_signed else (1.0, 0.0)
+    check(lib.cn_image_preprocess(_ptr(imgs), CN_U8 if imgs.dtype == torch.uint8 else CN_F32, _ptr(y), n, h, wd, c, oh, ow, mul, add,
+                                  _stream()), "cn_image_preprocess")
     return y
 
 

@@ -35,12 +35,15 @@ extern "C" {
 /* storage type of activation tensors (the `dt` arguments) */
 #define CN_F32 0
 #define CN_BF16 1        /* bfloat16 bits, round-to-nearest-even on store */
+#define CN_U8 2          /* uint8 pixels: the input of cn_image_preprocess only */
 
 /* activation codes for fused epilogues */
 #define CN_ACT_NONE 0
 #define CN_ACT_LRELU 1   /* keras LeakyReLU(alpha) / tf.nn.leaky_relu */
 #define CN_ACT_RELU 2
 #define CN_ACT_TANH 3
+#define CN_ACT_RELU6 4   /* min(max(v, 0), 6): keras ReLU(6.) of MobileNetV2 (keras_applications/mobilenet_v2.py) */
+#define CN_ACT_SIGMOID 5 /* 1 / (1 + exp(-v)): keras Dense(activation="sigmoid") */
 
 /* Geometry of one N-d convolution read as an implicit GEMM.  2-D uses nd=2, *_d = 1 (k_d=1,
  * s_d=1, dl_d=1, p_d=0).  Output position o, tap k reads v = o*s - p + k of the (virtually
@@ -398,6 +401,19 @@ int cn_maxpool_bwd(const void* x, const void* gy, void* gx, int n, int h, int w,
 /* AveragePooling2D((3,3), strides 1, padding "same") of keras.applications InceptionV3's pool branches (reference:
  * metrics/inception_distance.py:12, the FID/KID feature extractor); window cells outside the image are not counted [TF-2.1]. */
 int cn_avgpool3_same(const void* x, void* y, int n, int h, int w, int c, int dt, void* stream);
+/* ---- CelebA attribute classifier (confignet/metrics/celeba_attribute_prediction.py: keras.applications.MobileNetV2) -------
+ * Depthwise 3x3 convolution, depth_multiplier 1, fp32 NHWC: y (n, ceil(h/s), ceil(wd/s), c) = act(dw(x, w) + bias), w the Keras
+ * DepthwiseConv2D kernel (3, 3, c, 1), bias per channel (NULL: none; the folded BatchNormalization).  Replaces the
+ * DepthwiseConv2D -> BatchNormalization -> ReLU(6.) of keras_applications/mobilenet_v2.py _inverted_res_block; stride 1 or 2,
+ * padding TF "same" (for k = 3 the same pads as the ZeroPadding2D(correct_pad) + VALID of the stride-2 layers). */
+int cn_dwconv3x3_fwd(const float* x, const float* w, const float* bias, float* y, int n, int h, int wd, int c, int stride,
+                     int act, float slope, void* stream);
+/* One pass from a batch of images (n, h, w, c), x_dt CN_U8 or CN_F32, to the classifier input y (n, oh, ow, c) fp32:
+ * v = x * in_mul + in_add, bilinear resampling to (oh, ow) with half-pixel centres and edge clamping (cv2.resize INTER_LINEAR,
+ * computed in fp32 also for uint8 input), then keras mobilenet_v2.preprocess_input v / 127.5 - 1.  Replaces
+ * celeba_attribute_prediction.py:129-139 (the cv2.resize loop and preprocess_input of predict_attributes). */
+int cn_image_preprocess(const void* x, int x_dt, float* y, int n, int h, int wd, int c, int oh, int ow, float in_mul, float in_add,
+                        void* stream);
 /* y[...,j] = scale * x[...,perm[j]] + off[j] on 3-channel images: (x+1)*127.5 + "caffe"/VGGFace
  * preprocessing (perceptual_loss.py:52-61 ; real_encoder.py:24-25); bwd scatters back. */
 int cn_chan_affine3_fwd(const float* x, float* y, size_t pixels, const int* perm, float scale, const float* off, void* stream);

@@ -6,8 +6,10 @@
     python -m torch.distributed.run --nproc-per-node 8 train_confignet.py ...      # data parallel, one rank per GPU
 
 Dataset files are the reference's (`NeuralRendererDataset.save`: <name>.pck + <name>_imgs.dat).  `--synthetic N` replaces
-all three by seeded FFHQ-shaped noise sets of N images (no dataset can be downloaded here).  Metrics that need the
-attribute classifier / InceptionV3 are out of scope, so --attribute_classifier_path is accepted and ignored."""
+all three by seeded FFHQ-shaped noise sets of N images (no dataset can be downloaded here).  --attribute_classifier_path
+(a CelebaAttributeClassifier .json, relative to --data_dir when that is given; "none" or absent: no controllability
+metrics) enables the controllability metrics of the second stage; --beard_style_map_path (the
+synthetic data's beard_style_to_pca_map.json) adds the mustache configuration to them."""
 import argparse
 import os
 import sys
@@ -25,6 +27,7 @@ FLAGS = [
     ("--n_samples_for_metrics", dict(type=int, default=1000)),
     ("--synthetic", dict(type=int, default=0, help="use seeded synthetic datasets of this many images")),
     ("--resolution", dict(type=int, default=256, help="image size of the synthetic datasets")),
+    ("--beard_style_map_path", dict(default=None, help="beard_style_to_pca_map.json: adds the mustache controllability metric")),
 ]
 
 
@@ -45,6 +48,9 @@ def parse_args(argv):
         if args.data_dir is not None:
             paths = [os.path.join(args.data_dir, p) for p in paths]
         real, synth, val = (confignet.NeuralRendererDataset.load(p) for p in paths)
+    classifier = args.attribute_classifier_path
+    if classifier is not None and classifier.lower() != "none" and args.data_dir is not None:
+        classifier = os.path.join(args.data_dir, classifier)                                  # l.39-40
     log_dir = args.log_dir or args.output_dir
     config = confignet.confignet_utils.merge_configs(DEFAULT_CONFIG, {"batch_size": args.batch_size,
                                                                        "output_shape": tuple(real.imgs.shape[1:])})
@@ -56,10 +62,12 @@ def parse_args(argv):
     weights = first.get_weights()
 
     config["image_loss_weight"] *= 10                                  # l.67
+    if args.beard_style_map_path is not None:
+        config["beard_style_map_path"] = args.beard_style_map_path
     second = confignet.ConfigNet(config, seed=0)
     confignet.ConfigNetFirstStage.set_weights(second, weights)         # l.69: called unbound on the second-stage model
     # (the reference passes stage_1_training_steps here too, l.72; --stage_2_training_steps is parsed and unused)
-    second.train(real, synth, val, args.attribute_classifier_path, args.output_dir, log_dir,
+    second.train(real, synth, val, classifier, args.output_dir, log_dir,
                  n_steps=args.stage_1_training_steps, n_samples_for_metrics=args.n_samples_for_metrics)
     return second
 
