@@ -352,9 +352,8 @@ class ResNetTrunkFn(torch.autograd.Function):
         dev = gy.device
         params = enc._trunk_params()
         want_w = any(ctx.needs_input_grad[2:]) and not F._INPUT_GRADS_ONLY
-        sunk = want_w and ops.sink_for(params[0]) is not None
         # (a pass whose sink does not hold this network: nothing of this node may be deferred to that sink's join)
-        defer_prev, ops.DEFER_SLAB_SUMS = ops.DEFER_SLAB_SUMS, ops.DEFER_SLAB_SUMS and sunk
+        sunk = want_w and ops.sink_for(params[0]) is not None
         gwf = gsh = None
         if want_w:
             gwf = torch.empty(total, device=dev, dtype=torch.float32)    # every layer WRITES its part (accumulate=False)
@@ -368,7 +367,7 @@ class ResNetTrunkFn(torch.autograd.Function):
         def wgrad(ci, t_in, gu):
             o, shp = views[ci]
             if want_w:
-                ops.sink_conv_wgrad_to(t_in, gu, geom(ci, t_in), shp, gwf[o:o + int(np.prod(shp))].view(shp))
+                ops.sink_conv_wgrad_to(t_in, gu, geom(ci, t_in), shp, gwf[o:o + int(np.prod(shp))].view(shp), defer=sunk)
 
         def relu_bwd(ci, g, y, also=None):
             """g * (y > 0) and its channel sums into the shift gradient of layer ci (and of layer `also`: a block's shortcut
@@ -376,20 +375,11 @@ class ResNetTrunkFn(torch.autograd.Function):
             if not want_w:
                 return ops.act_bwd(g, y, ACT_RELU)
             gu, part = ops.act_bwd_partials(g, y, ACT_RELU)
-            ops.sum_rows_into(part, gsh[offs[ci]:offs[ci + 1]])
+            ops.sum_rows_into(part, gsh[offs[ci]:offs[ci + 1]], defer=sunk)
             if also is not None:
-                ops.sum_rows_into(part, gsh[offs[also]:offs[also + 1]])
+                ops.sum_rows_into(part, gsh[offs[also]:offs[also + 1]], defer=sunk)
             return gu
 
-        try:
-            return ResNetTrunkFn._walk(ctx, gy, enc, wf, offs, saved, views, gwf, gsh, want_w, sunk, params, geom, wgrad, relu_bwd,
-                                       seg9, blocks, a, rs, bm)
-        finally:
-            ops.DEFER_SLAB_SUMS = defer_prev
-
-    @staticmethod
-    def _walk(ctx, gy, enc, wf, offs, saved, views, gwf, gsh, want_w, sunk, params, geom, wgrad, relu_bwd, seg9, blocks, a, rs, bm):
-        from .. import ops
         # walk the blocks backwards; `pos` indexes the saved activations
         g = gy.contiguous()
         layout = []                                  # (first conv index of the block, has conv shortcut) in forward order

@@ -69,7 +69,7 @@ class ConvFn(Function):
         want_w = ctx.needs_input_grad[1] and not _INPUT_GRADS_ONLY
         want_b = ctx.has_bias and ctx.needs_input_grad[2] and not _INPUT_GRADS_ONLY
         # inside nn.backward_into_arenas: filter / bias gradients are added straight into their gradient-arena slots by the
-        # kernels, on the sink's side stream (ops.grad_sink); autograd then sees None for them
+        # kernels, on the calling stream (ops.grad_sink); autograd then sees None for them
         w_slot = ops.sink_for(w) if (first_order and want_w) else None
         b_slot = ops.sink_for(ctx.bias_ref) if (first_order and want_b and ctx.bias_ref is not None) else None
         if ctx.act != ACT_NONE:

@@ -143,7 +143,7 @@ def backward_into_arenas(loss, nets, extra=(), grad_outputs=None, accumulate=Fal
     Uses autograd.grad + one multi-tensor copy instead of .backward(): AccumulateGrad nodes are bound to the
     stream they were created on, which breaks HIP-graph capture of a step on a capture stream.
     Round 3: the arenas are cleared by one launch each and every gradient is ADDED -- the convolution / dense weight and bias
-    gradients by their own kernels, on a side stream off the backward chain (ops.grad_sink), the rest (norm parameters, free
+    gradients by their own kernels, on the calling stream (ops.grad_sink), the rest (norm parameters, free
     variables) by one multi-tensor add of what autograd returns.
     Weights switched off with requires_grad_(False) (a variable the caller leaves out of the reference's
     trainable list, e.g. the expression slice of fine_tune_on_img(force_neutral_expression=True)) get a zero

@@ -154,7 +154,6 @@ def geom_in_shape(g, upsampled=False):
     return (g.n, g.in_h << u, g.in_w << u, g.cin)
 
 
-_CACHE_SINGLE = False      # A/B: one derived copy per filter, re-derived whenever the other branch used it
 _keepalive = None        # a list while an InferenceGraph is captured: every derived filter copy the capture references
 
 
@@ -192,7 +191,7 @@ def _weight_cache_lookup(w, slot, make):
     # one entry PER STREAM (a dict): the two branches of a forked step use the same generator / regressor filters alternately --
     # forward on one stream, forward on the other, then the two backward passes -- and a single entry made each of them derive its
     # copy again (the key holds the stream, so the other branch's entry never matched and was replaced)
-    if isinstance(c, dict) and not _CACHE_SINGLE:
+    if isinstance(c, dict):
         e = c.get(stream)
         if e is not None and e[0] == key:
             return e[1]
@@ -534,14 +533,10 @@ def _c3_partials():
     return _C3_PARTS[0]
 
 
-_EXP_NO_WGRAD = False       # timing experiment only (wrong gradients): filter gradients not launched
-
-
-def conv_wgrad(x, gy, g, w_shape, out=None, accumulate=True):
+def conv_wgrad(x, gy, g, w_shape, out=None, accumulate=True, defer=True):
     """out: ADD the filter gradient to this tensor (a slot of a gradient arena, see grad_sink) instead of returning a new one;
-    out with accumulate=False: WRITE it there (an uninitialised scratch the caller owns: the folded ResNet-50's packed gradients)."""
-    if _EXP_NO_WGRAD:
-        return out if out is not None else torch.empty(w_shape, device=x.device, dtype=torch.float32)
+    out with accumulate=False: WRITE it there (an uninitialised scratch the caller owns: the folded ResNet-50's packed gradients).
+    defer=False: complete in `out` when this returns, also inside a grad_sink (no slab reduction left to its join)."""
     gw = out if out is not None else zero_pool_alloc(w_shape, x.device)
     pre = gw is not None and (accumulate or out is None)
     if gw is None:
@@ -572,14 +567,14 @@ def conv_wgrad(x, gy, g, w_shape, out=None, accumulate=True):
     # caller-owned workspace for the partial filters of the kernel's row splits (0 bytes: a single split / the fall-back kernel)
     nbytes = int(lib.cn_conv_wgrad_workspace_bytes(ctypes.byref(g)))
     ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32) if nbytes else None
-    if nbytes and out is not None and _SINK is not None and DEFER_SLAB_SUMS:
+    if nbytes and out is not None and _SINK is not None and defer:
         # inside a backward pass (grad_sink): the row slices' slabs stay in `ws` and the pass adds the slabs of ALL its filter
         # gradients with one grouped launch at its join (grad_sink.join) instead of one reduction launch per layer on the chain
         parts = ctypes.c_int(0)
         check(lib.cn_conv_wgrad_ws_slabs(ctypes.byref(g), _ptr(x), _ptr(gy), _fptr(gw), int(pre), _ptr(ws), nbytes, ctypes.byref(parts),
                                          _stream()), "cn_conv_wgrad_ws_slabs")
         if parts.value:
-            _SINK.setdefault("slabs", []).append((ws, gw, parts.value, gw.numel(), int(pre)))
+            _SINK.slabs.append((ws, gw, parts.value, gw.numel(), int(pre)))
         return gw
     check(lib.cn_conv_wgrad_ws(ctypes.byref(g), _ptr(x), _ptr(gy), _fptr(gw), int(pre), _ptr(ws), nbytes, _stream()), "cn_conv_wgrad_ws")
     return gw
@@ -589,29 +584,76 @@ def conv_wgrad(x, gy, g, w_shape, out=None, accumulate=True):
 # gradient sink: while nn.backward_into_arenas runs a backward pass, the filter / dense-weight / bias gradients are ADDED by
 # their kernels straight into the weights' slots of the networks' gradient arenas (tf.GradientTape sums the contributions of
 # every use of a variable: here the wgrad kernels' own accumulate mode does, not autograd's add kernels and not a copy pass
-# afterwards).  GRAD_SINK = False: gradients through autograd as before.
-# Nothing downstream of a weight gradient is on the backward chain, so the sinks CAN run on a side stream that forks off the
-# chain (WGRAD_FORK = True, one cross-stream edge per WGRAD_GROUP launches, joined at the end of the pass; all sinks share
-# ONE side stream, so accumulations into one slot never race).  Measured and left OFF: with the filter gradients not
-# launched at all the iteration drops 49.8 -> 42.3 ms (the bound of the idea), but the forked graphs replay SLOWER than the
-# single chain -- 63.6 ms with an edge per 8 launches, 53.2 per 32, 52.3 with one fork at the end of the pass, against
-# 49.5 unforked: the four hardware queues already carry the iteration's four concurrent lines, a fifth branch takes a queue
-# from one of them (GPU_MAX_HW_QUEUES = 6 / 8 make every variant worse: 61 - 87 ms).
+# afterwards).  Every sink launch runs on the stream that calls it; the pass' small reductions are queued and launched
+# grouped at its join.  GRAD_SINK = False: gradients through autograd as before.
+# Forking the filter gradients off the backward chain (a fifth stream, or the other branch's stream) was measured and
+# rejected: DESIGN.md section 3.
 # ---------------------------------------------------------------------------------------------
 GRAD_SINK = True
-DEFER_SLAB_SUMS = True     # the filter gradients' slab reductions of a backward pass as ONE grouped launch at its join (False: one per layer)
-WGRAD_FORK = False
-# Round 4 experiment, OFF (WGRAD_BALANCE = True switches it on): load balancing between the TWO streams a forked step already has.
-# The backward pass of the generator step runs as two chains -- the real branch (VGG, generator, the whole ResNet-50 encoder) on
-# the model's branch stream, the synthetic branch on the calling stream -- and the real chain is the longer one by the encoder's
-# backward.  Filter / dense-weight gradients are leaves of the tape (nothing on a chain waits for them), so the sink launches
-# issued on a stream other than the one the pass was started on were queued and handed to the calling stream in groups (one
-# cross-stream edge per WGRAD_GROUP launches; no extra stream, no extra hardware queue -- what sank WGRAD_FORK).  Measured
-# (profiles/round4_schedule_experiments.txt): 335 / 327 / 334 images/s with an edge per 8 / 4 / 16 launches against 352 without --
-# every cross-branch edge inside a captured graph costs more than the idle tail of the shorter chain it would fill.
-WGRAD_BALANCE = False
-_SINK = None              # {"slots": {data_ptr: grad view}, "side": stream | None, "keep": [...], "used": bool}
-_SIDE_STREAMS = {}
+_SINK = None              # the _Sink of the backward pass in flight (grad_sink), else None
+
+
+def sink_rounds(jobs, key):
+    """`jobs` split into rounds (lists, each in the original order): jobs with the same key(job) go into successive rounds,
+    every other job into the first."""
+    rounds, seen = [], {}
+    for job in jobs:
+        k = key(job)
+        r = seen.get(k, 0)
+        seen[k] = r + 1
+        if r == len(rounds):
+            rounds.append([])
+        rounds[r].append(job)
+    return rounds
+
+
+class _Sink:
+    """What one backward pass holds: the arena slots of its weights and the work queued for its join."""
+
+    def __init__(self, params):
+        self.slots = {p.data_ptr(): p.grad for p in params if p.grad is not None}
+        self.touched = []       # every stream a sink launch was issued on (a forked step has two)
+        self.slabs = []         # (src, dst, parts, count, accumulate): ordered slab sums -> cn_sum_parts_grouped
+        self.depth = []         # (a, b, slot): dense weight gradients a^T b -> cn_gemm_depth_grouped
+        self.upfold = {}        # slot pointer -> (class-filter gradient scratch, geometry, filter shape, slot)
+        self.post = []          # functions run once everything above has been issued
+        self.post_keep = []     # the tensors they read
+
+    def note_stream(self):
+        cur = torch.cuda.current_stream()
+        if all(cur != s_ for s_ in self.touched):
+            self.touched.append(cur)
+
+
+def _sum_slabs_grouped(slabs):
+    # every filter gradient of the pass that split its rows: (slabs, destination, parts, count, accumulate) -> ONE launch
+    # per 80 of them, each reduced in slice order exactly as cn_conv_wgrad_ws would have (same bits)
+    # (a weight used more than once in the pass -- the generator runs twice in the generator step -- has several jobs
+    # with ONE destination: they go into successive launches, in the order of their filter gradients, so that the adds
+    # into one element keep a fixed order; typically two or three launches for ~70 reductions)
+    for batch in sink_rounds(slabs, lambda job: job[1].data_ptr()):
+        jobs = (CnSumJob * len(batch))()
+        for q, (ws, dst, parts, count, acc) in zip(jobs, batch):
+            q.src, q.dst, q.count, q.parts, q.accumulate = ws.data_ptr(), dst.data_ptr(), count, parts, acc
+        check(lib.cn_sum_parts_grouped(jobs, len(batch), _stream()), "cn_sum_parts_grouped")
+
+
+def _gemm_depth_grouped(depth):
+    for batch in sink_rounds(depth, lambda job: job[2].data_ptr()):     # (same-destination jobs in successive launches, as above)
+        jobs = (CnDepthJob * len(batch))()
+        for q, (a, b, slot) in zip(jobs, batch):
+            q.a, q.b, q.c = a.data_ptr(), b.data_ptr(), slot.data_ptr()
+            q.m, q.n, q.k, q.lda, q.ldb, q.ldc = a.shape[1], b.shape[1], a.shape[0], a.shape[1], b.shape[1], b.shape[1]
+        check(lib.cn_gemm_depth_grouped(jobs, len(batch), _stream()), "cn_gemm_depth_grouped")
+
+
+def _release_operands(cur, others, operands):
+    """After launches on `cur` that read tensors produced on the streams `others`."""
+    if not torch.cuda.is_current_stream_capturing():      # (eager dispatch: the operands were allocated on the stream of
+        for t in operands:                                # their producer, not on this one)
+            t.record_stream(cur)
+    for s_ in others:                         # a stream that produced operands must not run ahead of these launches: a block
+        s_.wait_stream(cur)                   # the allocator hands out again after the join would be overwritten under them
 
 
 class grad_sink:
@@ -621,96 +663,39 @@ class grad_sink:
     def __enter__(self):
         global _SINK
         assert _SINK is None, "nested gradient sinks"
-        if not GRAD_SINK or not self.params:
-            return self
-        dev = self.params[0].device
-        side = None
-        if WGRAD_FORK:
-            side = _SIDE_STREAMS.get(dev)
-            if side is None:
-                side = _SIDE_STREAMS[dev] = torch.cuda.Stream(device=dev)
-        _SINK = {"slots": {p.data_ptr(): p.grad for p in self.params if p.grad is not None}, "side": side, "keep": [], "used": False,
-                 "home": torch.cuda.current_stream(dev)}
+        if GRAD_SINK and self.params:
+            _SINK = _Sink(self.params)
         return self
 
     def join(self):
-        """Order the calling stream after everything the sinks launched; drop the tensors kept alive for them."""
+        """Order the calling stream after everything the sinks launched and issue, on it, what the pass queued for its end."""
         st = _SINK
-        _sink_flush()
-        _balance_flush()
-        if st is not None and st["side"] is not None and st["used"]:
-            torch.cuda.current_stream().wait_stream(st["side"])
-        if st is not None:
-            cur = torch.cuda.current_stream()
-            touched = st.pop("touched", [])
-            for s_ in touched:                          # every stream a sink launched on (a forked step has two) before anything
-                if s_ != cur:                           # below reads or adds to the arenas on the calling stream
-                    cur.wait_stream(s_)
-            slabs = st.pop("slabs", [])
-            if slabs:
-                # every filter gradient of the pass that split its rows: (slabs, destination, parts, count, accumulate) -> ONE launch
-                # per 80 of them, each reduced in slice order exactly as cn_conv_wgrad_ws would have (same bits)
-                # (a weight used more than once in the pass -- the generator runs twice in the generator step -- has several jobs
-                # with ONE destination: they go into successive launches, in the order of their filter gradients, so that the adds
-                # into one element keep a fixed order; typically two or three launches for ~70 reductions)
-                rounds, seen = [], {}
-                for job in slabs:
-                    r = seen.get(job[1].data_ptr(), 0)
-                    seen[job[1].data_ptr()] = r + 1
-                    if r == len(rounds):
-                        rounds.append([])
-                    rounds[r].append(job)
-                for batch in rounds:
-                    jobs = (CnSumJob * len(batch))()
-                    for q, (ws, dst, parts, count, acc) in zip(jobs, batch):
-                        q.src, q.dst, q.count, q.parts, q.accumulate = ws.data_ptr(), dst.data_ptr(), count, parts, acc
-                    check(lib.cn_sum_parts_grouped(jobs, len(batch), _stream()), "cn_sum_parts_grouped")
-            depth = st.pop("depth", [])
-            if depth:
-                rounds, seen = [], {}                 # (same-destination jobs in successive launches, as above)
-                for job in depth:
-                    r = seen.get(job[2].data_ptr(), 0)
-                    seen[job[2].data_ptr()] = r + 1
-                    if r == len(rounds):
-                        rounds.append([])
-                    rounds[r].append(job)
-                for batch in rounds:
-                    jobs = (CnDepthJob * len(batch))()
-                    for q, (a, b, slot) in zip(jobs, batch):
-                        q.a, q.b, q.c = a.data_ptr(), b.data_ptr(), slot.data_ptr()
-                        q.m, q.n, q.k, q.lda, q.ldb, q.ldc = a.shape[1], b.shape[1], a.shape[0], a.shape[1], b.shape[1], b.shape[1]
-                    check(lib.cn_gemm_depth_grouped(jobs, len(batch), _stream()), "cn_gemm_depth_grouped")
-            if slabs or depth:
-                if not torch.cuda.is_current_stream_capturing():      # (eager dispatch: the operands were allocated on the stream of
-                    for t in [j[0] for j in slabs] + [t for j in depth for t in j[:2]]:     # their producer, not on this one)
-                        t.record_stream(cur)
-                for s_ in touched:                    # a stream that produced operands must not run ahead of these launches: a block
-                    if s_ != cur:                     # the allocator hands out again after the join would be overwritten under them
-                        s_.wait_stream(cur)
-            for gw2, g, w_shape, slot in st.pop("upfold", {}).values():
-                upfold_wgrad(gw2, g, w_shape, out=slot, single_writer=True)
-            post = st.pop("post", [])
-            for fn in post:                           # launches that read what the grouped reductions above have just completed
-                fn()                                  # (the folded ResNet-50's parameter gradients: cn_bn_fold_bwd)
-            post_keep = st.pop("post_keep", [])
-            if post:
-                if not torch.cuda.is_current_stream_capturing():
-                    for t in post_keep:
-                        t.record_stream(cur)
-                for s_ in touched:
-                    if s_ != cur:
-                        s_.wait_stream(cur)
-        if st is not None:
-            st["keep"].clear()
-            st["used"] = False
+        if st is None:
+            return
+        cur = torch.cuda.current_stream()
+        others = [s_ for s_ in st.touched if s_ != cur]
+        for s_ in others:                             # every stream a sink launched on (a forked step has two) before anything
+            cur.wait_stream(s_)                       # below reads or adds to the arenas on the calling stream
+        slabs, depth, upfold, post, post_keep = st.slabs, st.depth, st.upfold, st.post, st.post_keep
+        st.touched, st.slabs, st.depth, st.upfold, st.post, st.post_keep = [], [], [], {}, [], []
+        _sum_slabs_grouped(slabs)
+        _gemm_depth_grouped(depth)
+        if slabs or depth:
+            _release_operands(cur, others, [j[0] for j in slabs] + [t for j in depth for t in j[:2]])
+        for gw2, g, w_shape, slot in upfold.values():
+            upfold_wgrad(gw2, g, w_shape, out=slot, single_writer=True)
+        for fn in post:                               # launches that read what the grouped reductions above have just completed
+            fn()                                      # (the folded ResNet-50's parameter gradients: cn_bn_fold_bwd)
+        if post:
+            _release_operands(cur, others, post_keep)
+        if st.slabs or st.depth or st.upfold or st.post:                          # nothing runs after this point: work queued by a post function would be lost
+            raise RuntimeError("a sink_post function queued work on the gradient sink after its join")
 
     def __exit__(self, exc_type, exc, tb):
         global _SINK
         try:
-            if exc_type is None:
+            if exc_type is None:                    # (the pass raised: no scatter work on half-written scratch, just let go)
                 self.join()
-            elif _SINK is not None:                 # the pass raised: no scatter work on half-written scratch, just let go
-                _SINK["keep"].clear()
         finally:
             _SINK = None                            # a failed pass must not leave every later one dying on "nested gradient sinks"
 
@@ -719,97 +704,32 @@ def sink_for(w):
     """The gradient-arena slot of weight w if a sink is active for it (else None)."""
     if _SINK is None or w is None:
         return None
-    return _SINK["slots"].get(w.data_ptr())
-
-
-WGRAD_GROUP = 8      # sink launches per fork off the backward chain
-
-
-def _sink_flush():
-    """Fork the side stream off the calling stream HERE and launch everything queued since the last fork on it."""
-    st = _SINK
-    if st is None or not st.get("queue"):
-        return
-    queue, st["queue"] = st["queue"], []
-    side = st["side"]
-    for s_ in st.pop("streams", ()):          # every stream a queued launch's operands were produced on (a forked step has two)
-        side.wait_stream(s_)
-    st["used"] = True
-    with torch.cuda.stream(side):
-        for fn in queue:
-            fn()
-
-
-def _balance_flush():
-    """WGRAD_BALANCE: launch the sinks queued from branch streams on the stream the backward pass was started on, ordered after
-    what their operands' streams have been issued so far."""
-    st = _SINK
-    if st is None or not st.get("bq"):
-        return
-    queue, st["bq"] = st["bq"], []
-    home = st["home"]
-    for s_ in st.pop("bq_streams", ()):
-        home.wait_stream(s_)
-    with torch.cuda.stream(home):
-        for fn in queue:
-            fn()
-
-
-def _sink_run(fn, keep):
-    """Run one sink launch: immediately on the calling stream (no fork), or queued for the side stream -- every WGRAD_GROUP
-    launches one cross-stream edge (an edge per layer made the captured graph a ladder that replayed 35 % slower than the
-    single chain: 49.3 -> 66.5 ms).  `keep`: the tensors the launch reads; they stay alive until the join."""
-    st = _SINK
-    if st is not None:
-        cur0 = torch.cuda.current_stream()
-        if all(cur0 != s_ for s_ in st.setdefault("touched", [])):
-            st["touched"].append(cur0)
-    if st is not None and st["side"] is None and WGRAD_BALANCE and not DETERMINISTIC and cur0 != st["home"]:
-        capturing = torch.cuda.is_current_stream_capturing()
-        for t in keep:
-            if t is not None:
-                st["keep"].append(t)
-                if not capturing:
-                    t.record_stream(st["home"])       # (eager dispatch: the block was allocated on the branch stream)
-        st.setdefault("bq", []).append(fn)
-        if all(cur0 != s_ for s_ in st.setdefault("bq_streams", [])):
-            st["bq_streams"].append(cur0)
-        if len(st["bq"]) >= WGRAD_GROUP:
-            _balance_flush()
-        return
-    if st is None or st["side"] is None:
-        fn()
-        return
-    st["keep"].extend(t for t in keep if t is not None)
-    st.setdefault("queue", []).append(fn)
-    cur = torch.cuda.current_stream()
-    if all(cur != s_ for s_ in st.setdefault("streams", [])):
-        st["streams"].append(cur)
-    if len(st["queue"]) >= WGRAD_GROUP:
-        _sink_flush()
+    return _SINK.slots.get(w.data_ptr())
 
 
 def sink_conv_wgrad(x, gy, g, w_shape, slot):
-    _sink_run(lambda: conv_wgrad(x, gy, g, w_shape, out=slot), (x, gy))
+    if _SINK is not None:
+        _SINK.note_stream()
+    conv_wgrad(x, gy, g, w_shape, out=slot)
 
 
-def sink_conv_wgrad_to(x, gy, g, w_shape, dst):
+def sink_conv_wgrad_to(x, gy, g, w_shape, dst, defer=True):
     """The filter gradient WRITTEN (not added) into the caller's scratch `dst`, launched like a sink (a leaf of the pass)."""
-    _sink_run(lambda: conv_wgrad(x, gy, g, w_shape, out=dst, accumulate=False), (x, gy))
+    if _SINK is not None:
+        _SINK.note_stream()
+    conv_wgrad(x, gy, g, w_shape, out=dst, accumulate=False, defer=defer)
 
 
 def sink_post(fn, keep=()):
     """Run fn() once every sink launch of the pass -- the deferred grouped reductions included -- has been issued: at the join of
-    the active gradient sink, on the stream that joins; immediately without one."""
+    the active gradient sink, on the stream that joins; immediately without one.  fn must not queue work on the sink."""
     st = _SINK
     if st is None:
         fn()
         return
-    cur0 = torch.cuda.current_stream()
-    if all(cur0 != s_ for s_ in st.setdefault("touched", [])):
-        st["touched"].append(cur0)
-    st.setdefault("post_keep", []).extend(t for t in keep if t is not None)
-    st.setdefault("post", []).append(fn)
+    st.note_stream()
+    st.post_keep.extend(t for t in keep if t is not None)
+    st.post.append(fn)
 
 
 def bn_fold_bwd(seg9, blocks, gwf, gshift, arena, a, rs, bm, gout):
@@ -823,29 +743,27 @@ def sink_upfold_wgrad(gy, x, g2, wd_shape, g, w_shape, slot):
     in the generator step) is accumulated into one scratch by the filter-gradient kernel (atomics: any stream), and scattered
     back to the k taps ONCE, at the join of the pass, by a single writer (10 atomic scatters of up to 172 us -> 5 plain ones)."""
     st = _SINK
-    pend = st.setdefault("upfold", {})
-    ent = pend.get(slot.data_ptr())
+    ent = st.upfold.get(slot.data_ptr())
     if ent is None:
         gw2 = zero_pool_alloc(wd_shape, x.device)
         if gw2 is None:
             gw2 = torch.zeros(wd_shape, device=x.device, dtype=torch.float32)
-        ent = pend[slot.data_ptr()] = (gw2, g, w_shape, slot)
-    gw2 = ent[0]
-    _sink_run(lambda: conv_wgrad(gy, x, g2, wd_shape, out=gw2), (x, gy))
+        ent = st.upfold[slot.data_ptr()] = (gw2, g, w_shape, slot)
+    st.note_stream()
+    conv_wgrad(gy, x, g2, wd_shape, out=ent[0])
 
 
 def sink_gemm(a, b, slot, trans_a=False, trans_b=False):
     st = _SINK
-    if (st is not None and DEFER_SLAB_SUMS and trans_a and not trans_b and a.shape[0] <= 32 and a.dtype == torch.float32
-            and b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous() and slot.is_contiguous()):
-        # a dense layer's weight gradient x^T gy over a batch of <= 32 rows: a leaf of the pass -- queued for ONE grouped launch at
-        # the pass' join (grad_sink.join -> cn_gemm_depth_grouped) instead of a launch of its own on the backward chain
-        cur0 = torch.cuda.current_stream()
-        if all(cur0 != s_ for s_ in st.setdefault("touched", [])):
-            st["touched"].append(cur0)
-        st.setdefault("depth", []).append((a, b, slot))
-        return
-    _sink_run(lambda: gemm_acc(a, b, slot, trans_a, trans_b), (a, b))
+    if st is not None:
+        st.note_stream()
+        if (trans_a and not trans_b and a.shape[0] <= 32 and a.dtype == torch.float32 and b.dtype == torch.float32
+                and a.is_contiguous() and b.is_contiguous() and slot.is_contiguous()):
+            # a dense layer's weight gradient x^T gy over a batch of <= 32 rows: a leaf of the pass -- queued for ONE grouped launch at
+            # the pass' join (grad_sink.join -> cn_gemm_depth_grouped) instead of a launch of its own on the backward chain
+            st.depth.append((a, b, slot))
+            return
+    gemm_acc(a, b, slot, trans_a, trans_b)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1301,23 +1219,19 @@ def act_bwd_bias(gy, y, act, slope=0.0, sink=None):
     return gx, (gb.sum(0) if rep > 1 else gb.reshape(-1))
 
 
-def sum_rows_into(partial, dst, accumulate=True, side=True):
-    """dst[c] (+)= sum_r partial[r][c] (cn_sum_rows_into); under a grad_sink on its side stream (off the backward chain)."""
+def sum_rows_into(partial, dst, accumulate=True, defer=True):
+    """dst[c] (+)= sum_r partial[r][c] (cn_sum_rows_into), on the calling stream; under a grad_sink the sum joins the pass' grouped
+    reduction launch unless defer=False."""
     rows, c = partial.shape
-    if side and accumulate and _SINK is not None and DEFER_SLAB_SUMS and partial.dtype == torch.float32 and partial.is_contiguous():
-        # a leaf of the backward pass: joins the pass' grouped reduction launch (grad_sink.join) -- dst[c] += sum_r partial[r][c] is
-        # the ordered slab sum of `rows` parts of c floats; flag 2 keeps the serial order of cn_sum_rows_into for any row count
-        st = _SINK
-        cur0 = torch.cuda.current_stream()
-        if all(cur0 != s_ for s_ in st.setdefault("touched", [])):
-            st["touched"].append(cur0)
-        st.setdefault("slabs", []).append((partial, dst, rows, c, 1 | 2))
-        return
-    fn = lambda: check(lib.cn_sum_rows_into(_fptr(partial), _fptr(dst), rows, c, int(accumulate), _stream()), "cn_sum_rows_into")
-    if side:
-        _sink_run(fn, (partial,))
-    else:
-        fn()
+    st = _SINK
+    if st is not None:
+        st.note_stream()
+        if defer and accumulate and partial.dtype == torch.float32 and partial.is_contiguous():
+            # a leaf of the backward pass: joins the pass' grouped reduction launch (grad_sink.join) -- dst[c] += sum_r partial[r][c] is
+            # the ordered slab sum of `rows` parts of c floats; flag 2 keeps the serial order of cn_sum_rows_into for any row count
+            st.slabs.append((partial, dst, rows, c, 1 | 2))
+            return
+    check(lib.cn_sum_rows_into(_fptr(partial), _fptr(dst), rows, c, int(accumulate), _stream()), "cn_sum_rows_into")
 
 
 def bias_grad(gy, sink=None):
@@ -1327,7 +1241,7 @@ def bias_grad(gy, sink=None):
         return nc_reduce(gy, None, want_dot=False, per_channel=True)[0].reshape(-1)
     c = gy.shape[-1]
     rows = gy.numel() // c
-    if rows <= 64 and gy.dtype == torch.float32 and _SINK is not None and DEFER_SLAB_SUMS:
+    if rows <= 64 and gy.dtype == torch.float32 and _SINK is not None:
         # a dense layer's bias gradient over a batch of a few rows: the rows ARE the slabs of the pass' grouped reduction
         # (grad_sink.join) -- no launch of its own
         sum_rows_into(gy.reshape(rows, c), sink)

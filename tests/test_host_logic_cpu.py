@@ -1,5 +1,5 @@
 """Host-side logic that needs no GPU: config merging, the shared Adam step counter, deferred optimizer calls
-(multi-rank graph dispatch), work-stream slot table."""
+(multi-rank graph dispatch), work-stream slot table, launch rounds of the gradient sink's join."""
 import math
 
 import pytest
@@ -60,6 +60,15 @@ def test_work_stream_slots():
     slots = ConfigNetFirstStage._WORK_SLOTS
     assert slots["g"] == slots["d"] and len({slots["main"], slots["d"], slots["sd"], slots["ld"]}) == 4
     assert max(slots.values()) == 3
+
+
+def test_sink_rounds_put_jobs_with_one_destination_into_successive_rounds():
+    """ops.grad_sink.join launches its queued jobs grouped, one launch per round: jobs with the same destination must land in
+    successive rounds in their original order (the adds into one element keep a fixed order), everything else in the first."""
+    from confignet_amd.ops import sink_rounds
+    dst = ["A", "B", "A", "C", "A", "B"]
+    assert sink_rounds(list(range(6)), lambda i: dst[i]) == [[0, 1, 3], [2, 5], [4]]
+    assert sink_rounds([], lambda i: i) == []
 
 
 def test_bench_launches_its_own_ranks_or_says_what_is_missing():

@@ -535,7 +535,7 @@ def test_first_stage_generator_step_and_adam():
 
 @pytest.mark.parametrize("stacked", [False, True])
 def test_second_stage_generator_step(stacked):
-    """stacked: ConfigNet.merge_generator_passes (CN_G_MERGE=1; off by default -- it measured slower end to end): one stacked
+    """stacked: ConfigNet.merge_generator_passes = True (off by default -- it measured slower end to end): one stacked
     generator / VGG pass for the synthetic and the real half, held to the same oracle comparison as the two-pass form."""
     from confignet_amd import ConfigNet
     from confignet_amd.confignet_first_stage import frozen

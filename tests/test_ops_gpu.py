@@ -1134,6 +1134,61 @@ def test_dense_weight_gradients_of_a_backward_pass_as_one_grouped_launch_give_th
             assert torch.equal(p.grad, r), (i, dims[i], float((p.grad - r).abs().max()))
 
 
+@pytest.mark.gpu
+def test_undeferred_sink_launches_are_complete_before_the_pass_joins():
+    """defer=False inside a backward pass (ops.grad_sink): sink_conv_wgrad_to on a geometry that splits its rows and sum_rows_into
+    behave as outside one -- the whole result is in the destination on the launching stream BEFORE the sink is left, nothing is
+    kept for its join (a node whose network the sink does not hold: ResNetTrunkFn) -- and has the bits of the call outside a sink."""
+    from confignet_amd import ops
+    from confignet_amd._lib import lib
+    gen = torch.Generator(device="cuda").manual_seed(57)
+    xs, k, cout = (8, 32, 32, 128), (3, 3), 128
+    g = ops.ConvSpec(k, stride=1).geom(xs, cout)
+    assert int(lib.cn_conv_wgrad_workspace_bytes(ctypes.byref(g))) > 0, "the case must split its rows"
+    x = torch.randn(xs, device="cuda", generator=gen)
+    gy = torch.randn(ops.geom_out_shape(g), device="cuda", generator=gen)
+    ws = k + (xs[-1], cout)
+    part = torch.randn(48, 200, device="cuda", generator=gen)
+    base = torch.randn(200, device="cuda", generator=gen)
+    ref_w = torch.full(ws, float("nan"), device="cuda")           # (a scratch the call WRITES: every element must be replaced)
+    ops.sink_conv_wgrad_to(x, gy, g, ws, ref_w)
+    ref_s = base.clone()
+    ops.sum_rows_into(part, ref_s)
+    assert not torch.isnan(ref_w).any()
+    p = torch.zeros(4, device="cuda").requires_grad_(True)
+    p.grad = torch.zeros_like(p)
+    got_w, got_s = torch.full(ws, float("nan"), device="cuda"), base.clone()
+    with ops.grad_sink([p]):
+        assert ops.sink_for(p) is not None
+        ops.sink_conv_wgrad_to(x, gy, g, ws, got_w, defer=False)
+        ops.sum_rows_into(part, got_s, defer=False)
+        seen_w, seen_s = got_w.clone(), got_s.clone()          # read on the launching stream, inside the pass
+    torch.cuda.synchronize()
+    assert torch.equal(seen_w, ref_w), float((seen_w - ref_w).abs().max())
+    assert torch.equal(seen_s, ref_s), float((seen_s - ref_s).abs().max())
+    assert torch.equal(got_w, ref_w) and torch.equal(got_s, ref_s)      # (and the join added nothing on top)
+
+
+@pytest.mark.gpu
+def test_work_queued_on_the_sink_by_a_post_function_is_refused():
+    """A sink_post function runs after the join has issued the pass' grouped launches: work it queues on the sink would never be
+    launched.  The join raises instead of dropping it (host-side, nothing is launched for the stray job), and the failed pass
+    leaves no sink behind."""
+    from confignet_amd import ops
+    gen = torch.Generator(device="cuda").manual_seed(58)
+    a = torch.randn(16, 64, device="cuda", generator=gen)
+    b = torch.randn(16, 32, device="cuda", generator=gen)
+    p = torch.zeros(64, 32, device="cuda").requires_grad_(True)
+    p.grad = torch.zeros_like(p)
+    with pytest.raises(RuntimeError, match="queued work on the gradient sink"):
+        with ops.grad_sink([p]):
+            ops.sink_post(lambda: ops.sink_gemm(a, b, p.grad, True, False))
+    with ops.grad_sink([p]):
+        assert ops.sink_for(p) is p.grad
+    torch.cuda.synchronize()
+    assert not p.grad.any()
+
+
 # ---------------------------------------------------------------------------------------------
 # round 6 (second half): the entry points behind the restructured tape, each against a float64 statement of what it computes
 # ---------------------------------------------------------------------------------------------
