@@ -54,6 +54,24 @@ int cn_fwd2(const CnConvGeom* gp, int cfg, int bt, const float* A, const float* 
             int act, float slope, int splits, long part_stride, int par, hipStream_t s, const float* res, double x_elems, double w_elems,
             float* stats = nullptr, int stats_mode = 0, float stats_slope = 0.f, int srows = 1, int sper = 1);
 void cn_fwd2_tune(int kb, int ns, int np);
+void cn_fwd2_grid(int cfg, long M, int N, int par, int splits, int grid[3]);      // the launch grid cn_fwd2 uses
+// igemm_conv.hip: the register-staged implicit-GEMM loop on tile cfg (anything but 0 / 1 / 3 / 4: 64 x 64), the same split-K protocol;
+// cn_igemm_fwd_thin: its 128 x 32 tile with guarded filter loads for parity-ordered data gradients into a thin (cout <= 4) image;
+// cn_igemm_wgrad: the filter gradient split over rows (wg_target: workgroups aimed at, 0 = default); cn_tiny_wgrad: the from-RGB
+// shapes (1x1, <= 4 channels on both sides), CN_EUNSUPPORTED without launching for every other geometry
+int cn_igemm_fwd(int cfg, const CnConvGeom& g, bool vec, int par, int splits, const float* x, const float* w, const float* bias, float* y,
+                 int act, float slope, hipStream_t s, int bt, long part_stride, const float* res);
+void cn_igemm_fwd_grid(int cfg, const CnConvGeom& g, bool vec, int par, int splits, int grid[3]);
+int cn_igemm_fwd_thin(const CnConvGeom& g, const float* x, const float* w, const float* bias, float* y, int act, float slope, hipStream_t s);
+int cn_igemm_wgrad(int cfg, const CnConvGeom& g, const float* x, const float* gy, float* gw, long wg_target, hipStream_t s);
+int cn_tiny_wgrad(const CnConvGeom& g, const float* x, const float* gy, float* gw, hipStream_t s);
+// Which launch a forward / data-gradient convolution gets (conv_dispatch.hip: plan_conv_fwd; the numbers are what cn_conv_fwd_plan
+// reports).  small_conv.hip launches everything before CN_ROUTE_FWD2 except CN_ROUTE_THIN_PAR_IGEMM.
+enum ConvRoute { CN_ROUTE_UP2K4_RGB = 0, CN_ROUTE_S2_IMAGE_DGRAD, CN_ROUTE_S1_IMAGE_DGRAD, CN_ROUTE_THIN_PAR_IGEMM, CN_ROUTE_THIN_COOP,
+                 CN_ROUTE_THIN, CN_ROUTE_C3, CN_ROUTE_C7S2, CN_ROUTE_FWD2, CN_ROUTE_IGEMM, CN_ROUTE_UNSUPPORTED };
+constexpr int CN_THIN_COOP_PX = 4;        // output pixels per thread of thin_conv_coop_kernel
+void cn_small_conv(int route, unsigned grid_x, const CnConvGeom& g, bool vec, int par, const void* x, int x_dt, const float* w,
+                   const float* bias, void* y, int y_dt, int act, float slope, hipStream_t s);
 int cn_fwd2_bf16(const CnConvGeom& g, int cfg, int flip, const void* x, const void* wb, const float* bias, void* y, int act, float slope,
                  int par, hipStream_t s);
 

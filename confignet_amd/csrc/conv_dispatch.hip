@@ -1,0 +1,488 @@
+// conv_dispatch.hip -- which launch a convolution gets (host code only).
+//
+// Every fp32 forward / data-gradient convolution is served in two steps: plan_conv_fwd decides the launch from the geometry and
+// the request alone (route, tile, K split, profile family, grid -- no HIP call, no pointer), run_conv_fwd performs it (one switch
+// over the route, one profile bracket, one launch check, the split-K protocol).  cn_conv_fwd_plan reports the plan without a
+// device.  The kernels live in small_conv.hip (thin and image-side layers), fwd2.hip (the LDS-DMA loop) and igemm_conv.hip (the
+// register-staged implicit-GEMM loop); the filter-gradient entries and the tuning hooks are at the end of this file.
+#include "common.h"
+
+#include "mma_tile.h"
+#include "conv_geom.h"
+
+// wgrad2.hip
+bool cn_wgrad2_ok(const CnConvGeom& g);
+size_t cn_wgrad2_workspace_floats(const CnConvGeom& g);
+int cn_wgrad2_family(const CnConvGeom& g);
+void cn_wgrad2_tune(int cfg, long wg_target);
+void cn_wgrad2_stages(int ns);
+int cn_wgrad2(const CnConvGeom& g, const float* x, const float* gy, float* gw, int accumulate, float* ws, hipStream_t s, int* parts_out = nullptr);
+
+namespace {
+
+int g_tune_cfg = -1;                 // cn_conv_tune (sweeps, tests): forced tile / split-K factor / filter-gradient workgroup target
+int g_tune_splits = 0;
+long g_tune_wg_blocks = 0;
+int g_fwd2_sel = -1;                 // cn_conv_loop_select override: 0 = keep the LDS-DMA loop (fwd2.hip) off
+constexpr int g_fwd2_min_nks = 1;    // the LDS-DMA loop takes reductions of MORE K steps than this
+constexpr int g_fwd2_min_c = 48;     // thinnest layer it takes
+
+// What the caller asks for, as far as the choice of the launch depends on it.  bt = 1: w is the original filter of the convolution
+// whose data gradient the geometry describes (see igemm_fwd_kernel); stats_mode: cn_conv_fwd_stats; x_dt / y_dt: storage types of
+// input and output (anything but fp32 on both sides: cn_conv_fwd_dt).
+struct ConvReq {
+    int bt, has_bias, act, has_res, stats_mode, x_dt, y_dt;
+};
+
+struct ConvPlan {
+    int route = CN_ROUTE_UNSUPPORTED;
+    int ret = CN_EUNSUPPORTED;       // what the request gets when nothing is launched (route == CN_ROUTE_UNSUPPORTED)
+    int cfg = -1;                    // tile of the implicit-GEMM numbering (FWD2 / IGEMM)
+    int splits = 1, par = 0;
+    bool vec = false;
+    bool plain = false;              // FWD2: a plain 1x1 product, no gather
+    int family = -1;                 // CN_FAM_* of the profile bracket; -1: the launch has none
+    int srows = 1, sper = 1;         // statistics: rows of one sample / of one parity class
+    int grid[3] = {0, 0, 0};
+};
+
+// The image-side layers: 3x3 / 7x7 convolutions OF the 3-channel fp32 image (output fp32 or bf16) and the data gradients of the 3x3
+// ones INTO it (output gradient fp32 or, stride 2 only, bf16).  CN_ROUTE_UNSUPPORTED: none of them.
+int image_route(const CnConvGeom& g, const ConvReq& q) {
+    const bool x32 = q.x_dt == CN_F32, y32 = q.y_dt == CN_F32, x16 = q.x_dt == CN_BF16, y16 = q.y_dt == CN_BF16;
+    if (x32 && (y32 || y16) && !q.bt && g.nd == 2 && g.cin == 3 && g.dl_h == 1 && g.dl_w == 1 && !g.up && g.cout > 4 && g.cout <= 64) {
+        if (g.k_h == 3 && g.k_w == 3 && g.s_h == g.s_w && (g.s_h == 1 || g.s_h == 2)) return CN_ROUTE_C3;
+        if (g.k_h == 7 && g.k_w == 7 && g.s_h == 2 && g.s_w == 2 && !q.has_res) return CN_ROUTE_C7S2;
+    }
+    if (y32 && g.nd == 2 && g.k_h == 3 && g.k_w == 3 && g.s_h == 1 && g.s_w == 1 && !g.up && g.cout == 3 && !q.has_bias &&
+        q.act == CN_ACT_NONE && g.p_h >= 0 && g.p_h <= 2 && g.p_w >= 0 && g.p_w <= 2) {
+        if ((x32 || x16) && g.dl_h == 2 && g.dl_w == 2 && g.cin == 48 && g.out_h <= 2 * g.in_h && g.out_w <= 2 * g.in_w) return CN_ROUTE_S2_IMAGE_DGRAD;
+        if (x32 && g.dl_h == 1 && g.dl_w == 1 && g.cin == 64) return CN_ROUTE_S1_IMAGE_DGRAD;
+    }
+    return CN_ROUTE_UNSUPPORTED;
+}
+
+// Pure: reads the geometry, the request, cn_det(), cn_cu_count() and the tuning overrides.
+ConvPlan plan_conv_fwd(const CnConvGeom& g, const ConvReq& q) {
+    ConvPlan p;
+    const long M = (long)g.n * g.out_d * g.out_h * g.out_w;
+    const bool res = q.has_res != 0, stats = q.stats_mode != 0;
+    const int bt = q.bt;
+    auto small = [&p](int route, int family, long grid_x) {      // a single launch of a small_conv.hip / thin kernel
+        p.route = route;
+        p.ret = CN_OK;
+        p.family = family;
+        p.grid[0] = (int)grid_x; p.grid[1] = p.grid[2] = 1;
+        return p;
+    };
+    auto refuse = [&p](int code) {                               // nothing is launched
+        p.ret = code;
+        return p;
+    };
+    const int img = image_route(g, q);
+    const long img_grid = img == CN_ROUTE_S2_IMAGE_DGRAD ? (long)g.n * cn_cdiv(g.in_h, 8) * cn_cdiv(g.in_w, 32)
+                                                         : (long)g.n * cn_cdiv(g.out_h, 8) * cn_cdiv(g.out_w, 32);
+    const int img_family = img == CN_ROUTE_C3 || img == CN_ROUTE_C7S2 ? CN_FAM_C3_FWD : CN_FAM_S2_IMAGE_DGRAD;
+    if (q.x_dt != CN_F32 || q.y_dt != CN_F32)        // mixed storage types: the image-side kernels or nothing
+        return img != CN_ROUTE_UNSUPPORTED ? small(img, img_family, img_grid) : p;
+    // res: only the unsplit implicit-GEMM launches carry the residual add in their epilogue -- anything else answers
+    // CN_EUNSUPPORTED before launching (the caller then adds it with a pass of its own)
+    if ((res || stats) && (g.cout <= 4 || g.cin == 3 || g.cout % 4 != 0)) return p;
+    // stats: the launch must be one that can carry the statistics in its epilogue -- the unsplit LDS-DMA loop with tiles inside one
+    // sample -- or nothing is launched
+    if (stats && (bt || cn_det() || g.cin % BK != 0)) return p;
+    // bt: only the vectorised implicit-GEMM path takes the original filter
+    if (bt && (g.cout <= 4 || g.cin % BK != 0 || g.cout % 4 != 0)) return p;
+    if (g.cout <= 4) {
+        p.vec = g.cin % 4 == 0;
+        p.par = parity_ordered(g);
+        const size_t lds = sizeof(float) * 4 * (size_t)g.k_d * g.k_h * g.k_w * g.cin;
+        if (lds > 64 * 1024) {
+            cn_set_error("thin conv: filter of %zu bytes does not fit the LDS stage", lds);
+            return refuse(CN_EINVAL);
+        }
+        const int T = g.k_d * g.k_h * g.k_w, CL = g.cin / 4;
+        const bool dl1 = g.dl_d * g.dl_h * g.dl_w == 1;
+        if (g.nd == 2 && g.up == 1 && g.k_h == 4 && g.k_w == 4 && g.s_h == 1 && g.s_w == 1 && g.dl_h == 1 && g.dl_w == 1 &&
+            g.cout == 3 && g.cin == 32 && g.p_h == 1 && g.p_w == 1 && g.out_h <= 2 * g.in_h && g.out_w <= 2 * g.in_w)
+            return small(CN_ROUTE_UP2K4_RGB, CN_FAM_THIN, (long)g.n * cn_cdiv(g.in_h, 8) * cn_cdiv(g.in_w, 16));
+        if (img != CN_ROUTE_UNSUPPORTED) return small(img, img_family, img_grid);          // (the two data gradients into the image)
+        if (p.par && g.cin % BK == 0 && q.act == CN_ACT_NONE) return small(CN_ROUTE_THIN_PAR_IGEMM, CN_FAM_FWD_128x32, cn_cdiv(M, 128));
+        if (p.vec && g.cout == 3 && CL >= 5 && CL <= 16 && T <= 32 && (p.par || dl1) && g.dl_d * g.dl_h * g.dl_w <= 8)
+            return small(CN_ROUTE_THIN_COOP, -1, cn_cdiv(M, (256 / (CL <= 8 ? 8 : 16)) * CN_THIN_COOP_PX));
+        return small(CN_ROUTE_THIN, -1, cn_cdiv(M, 256));
+    }
+    if (img != CN_ROUTE_UNSUPPORTED) return small(img, img_family, img_grid);              // (the two first layers)
+    if (g.cout % 4 != 0) {
+        cn_set_error("cout=%d: implicit-GEMM path needs cout %% 4 == 0", g.cout);
+        return refuse(CN_EINVAL);
+    }
+    const bool vec = g.cin % BK == 0;
+    const int par = parity_ordered(g) && vec;
+    // tile choice: the biggest tile that still gives >= 2 workgroups per CU (256 CUs)
+    const long t128 = (long)cn_cdiv(M, 128) * cn_cdiv(g.cout, 128);
+    const long t128x64 = (long)cn_cdiv(M, 128) * cn_cdiv(g.cout, 64);
+    int cfg;
+    long tiles;
+    if (g.cout <= 32) { cfg = 3; tiles = (long)cn_cdiv(M, 128) * cn_cdiv(g.cout, 32); }
+    else if (g.cout > 64 && t128 >= 512) { cfg = 0; tiles = t128; }
+    else if (t128x64 >= 512) { cfg = 1; tiles = t128x64; }
+    else { cfg = 2; tiles = (long)cn_cdiv(M, 64) * cn_cdiv(g.cout, 64); }
+    // cout = 96 / 192 (discriminator blocks 1-2 and the data gradients of blocks 2-3): a 128 x 96 tile wastes nothing
+    // where 128- or 64-wide tiles pad a quarter of their columns
+    if (g.cout % 96 == 0 && g.cout % 128 != 0 &&
+        (long)cn_cdiv(M, 128) * (g.cout / 96) >= (g.cout == 96 ? 256 : 384)) {
+        cfg = 4;
+        tiles = (long)cn_cdiv(M, 128) * (g.cout / 96);
+    }
+    // split-K for small outputs with a long reduction (ResNet stage 4/5, Conv3D at 4^3->8^3)
+    int splits = 1;
+    // (parity-ordered data gradients: tiles of the 4-tap class carry 4x the K of the 1-tap class, so more, smaller
+    // K slices also even out the load -- conv_tune.py dgrad: 123 -> 95 us at M=16384 N=192, 124 -> 104 us at M=4096 N=384)
+    const bool par_small = par && cfg == 2;          // 64 x 64 tiles of a parity-ordered data gradient
+    const long nks_total = vec ? (long)g.k_d * g.k_h * g.k_w * (g.cin / BK) : 0;
+    // a short reduction (<= 8 steps) is all prologue and epilogue: the narrower tile spreads the stores over twice the workgroups
+    if (cfg == 0 && vec && !par && nks_total <= 8) { cfg = 1; tiles = t128x64; }
+    // one workgroup per CU and a short reduction: the zero pass, the atomics and the separate bias / activation pass of a K
+    // split cost more than the idle SIMD slots they would fill (conv_tune.py: M=8192 K=512 N=128 31 -> 25 us unsplit)
+    const bool short_full = !par && tiles >= 256 && nks_total < 64;
+    if (vec && tiles < (par_small ? 1024 : 512) && !short_full) {
+        long nks = nks_total;
+        if (par) nks /= (long)g.dl_d * g.dl_h * g.dl_w;
+        long want = ((par_small ? 3072 : 1024) + tiles - 1) / tiles;      // aim at ~4 (12) workgroups per CU
+        if (want > 16) want = 16;
+        const long min_steps = par_small ? 8 : 16;   // average K steps per workgroup
+        if (want > nks / min_steps) want = nks / min_steps;
+        if (want > 1) splits = (int)want;
+    }
+    // The LDS-DMA main loop (fwd2.hip) keeps the matrix pipe fed from ONE workgroup per CU (its loads run NS steps ahead of the
+    // MFMAs and none of its instructions sits outside an MFMA's shadow), so it does not need the 4 workgroups per CU the
+    // register-staged loops are split for -- and every K split it avoids saves the zero pass, a tile of atomics per workgroup and
+    // the separate bias / activation pass (13 us of a 60 us launch at M = 4096, K = 2304, N = 256; scripts/dev/fwd2_sweep.py).
+    // (32 output channels: the 128 x 32 tile of the same loop, input channels from 32 up)
+    const bool n32 = g.cout == 32 && g.cin >= 32;
+    const bool fwd2_takes = g_fwd2_sel != 0 && vec && nks_total > g_fwd2_min_nks && ((g.cin >= g_fwd2_min_c && g.cout >= g_fwd2_min_c) || n32) &&
+                            g.dl_d <= 2 && g.dl_h <= 2 && g.dl_w <= 2 && (double)g.n * g.in_d * g.in_h * g.in_w * g.cin < 5.3e8 &&
+                            (double)g.k_d * g.k_h * g.k_w * g.cin * g.cout < 5.3e8;
+    if (fwd2_takes) {
+        const int T = g.k_d * g.k_h * g.k_w;
+        // a parity-ordered 1x1 data gradient (ResNet's strided projections) has ONE live class: only M / (dl_d dl_h dl_w) of
+        // its rows do any work, the tiles of the other classes store zeros and leave
+        const long Me = (par && T == 1) ? M / ((long)g.dl_d * g.dl_h * g.dl_w) : M;
+        long nks = nks_total;
+        if (par) nks /= (long)g.dl_d * g.dl_h * g.dl_w;
+        splits = 1;
+        // parity classes with the same number of live taps (k % dl == 0 on every axis: the upsample-folded layers' class filters)
+        // are one balanced launch; the data gradients of the stride-2 3x3 layers mix classes of 1 / 2 / 2 / 4 taps
+        const bool par_balanced = par && g.k_d % g.dl_d == 0 && g.k_h % g.dl_h == 0 && g.k_w % g.dl_w == 0;
+        if (n32) {
+            cfg = 3;
+            tiles = cn_cdiv(M, 128);
+        } else if (par && T > 1 && !par_balanced) {
+            // classes of 1 / 2 / 2 / 4 live taps (a quarter of the rows each): the 64 x 64 tile (128 x 96 for cout = 96 once it fills
+            // the chip twice), K slices only for the 64 x 64 tile, where they also even out the load between the classes
+            cfg = 2;
+            tiles = (long)cn_cdiv(M, 64) * cn_cdiv(g.cout, 64);
+            if (g.cout % 96 == 0 && g.cout % 64 != 0 && (long)cn_cdiv(M, 128) * (g.cout / 96) >= 512) {
+                cfg = 4;
+                tiles = (long)cn_cdiv(M, 128) * (g.cout / 96);
+            }
+            if (cfg == 2 && tiles < 1024) {
+                long want = (1536 + tiles / 2) / tiles;
+                if (want > 16) want = 16;
+                if (want > nks / 8) want = nks / 8;
+                if (want > 1) splits = (int)want;
+            }
+        } else {
+            // Tile and K split together from a cost model of the launch (microseconds): the workgroups of one CU share its matrix
+            // pipes, so a launch of W workgroups takes ceil(W / 256) workgroup lifetimes of (K steps) x (MFMA time of a step +
+            // what the tile leaves exposed: measured per tile, scripts/dev/fwd2_sweep.py), plus a fixed start / drain, plus --
+            // with a K split -- the zero pass, the separate bias / activation pass and one tile of atomics per workgroup.  What
+            // the thresholds of the register-staged loops could not see is the quantisation: 384 workgroups on 256 CUs take as
+            // long as 512.
+            // The 64 x 64 tile wins the tile sweep almost everywhere with this loop (16 accumulator registers and 32 KB of LDS: five
+            // workgroups per CU, so their barriers and fills interleave, and 4x finer load balance than a 128 x 128 tile); the one
+            // exception is cout = 96, where 64-wide tiles pad a quarter of their columns and the 128 x 96 tile pads nothing.
+            struct Cand { int cfg, bm, bn; double step_us; };
+            const Cand cands[2] = {{2, 64, 64, 0.265}, {4, 128, 96, 0.68}};
+            double best = 0.0;
+            bool have = false;
+            for (const Cand& c : cands) {
+                if (c.cfg == 4 && (g.cout % 96 != 0 || g.cout % 64 == 0 || (long)cn_cdiv(Me, 128) * (g.cout / 96) < 256)) continue;
+                const long tl = (long)cn_cdiv(Me, c.bm) * cn_cdiv(g.cout, c.bn);
+                const long smax = nks / 8 > 1 ? (nks / 8 > 16 ? 16 : nks / 8) : 1;
+                for (long s_ = 1; s_ <= smax; ++s_) {
+                    const double waves = (double)cn_cdiv(tl * s_, cn_cu_count());
+                    double t = 10.0 + waves * (double)cn_cdiv(nks, s_) * c.step_us * (waves == 1.0 ? 1.06 : 1.0);
+                    if (s_ > 1) t += 9.0 + (double)s_ * (double)M * g.cout * 4.0 / 6.0e6;
+                    // a split launch cannot carry the residual add / the statistics in its epilogue: the caller then runs a pass of
+                    // its own over y (read + write at ~3 TB/s, one more launch) -- priced here so that a fused request splits only
+                    // where the split still wins with that pass added
+                    if (s_ > 1 && (res || stats)) t += 5.0 + 2.0 * (double)M * g.cout * 4.0 / 3.0e6;
+                    if (!have || t < best) { have = true; best = t; cfg = c.cfg; tiles = tl; splits = (int)s_; }
+                }
+            }
+        }
+    }
+    if (g_tune_cfg >= 0) cfg = g_tune_cfg;                        // tuning overrides (cn_conv_tune; scripts/conv_sweep.py)
+    if (g_tune_splits > 0) splits = g_tune_splits;
+    if (res && splits > 1) return p;
+    if (stats) {
+        // rows of one sample (inside one parity class for class-major rows); every tile must lie inside one sample
+        const int qd = par ? g.out_d / g.dl_d : g.out_d, qh = par ? g.out_h / g.dl_h : g.out_h, qw = par ? g.out_w / g.dl_w : g.out_w;
+        p.srows = qd * qh * qw;
+        p.sper = par ? g.n * p.srows : (int)M;
+        if (!fwd2_takes || splits > 1 || cfg == 3 || p.srows % (cfg == 2 ? 64 : 128) != 0) return p;
+    }
+    if (cn_det() && splits > 1) {
+        // deterministic mode: the K splits write partial outputs into the stream's workspace (as many splits as it holds) and a
+        // second launch adds them in split order -- no atomics
+        const long cap = (long)(CN_DET_WS_FLOATS / ((size_t)M * g.cout));
+        if (splits > cap) splits = (int)cap;
+        if (splits <= 1 || !vec) splits = 1;
+    }
+    // the LDS-DMA main loop; everything it does not take (K or cout no multiple of 16 / 4, thin layers, > 2 GiB operands, a forced
+    // 128 x 32 tile on more than 32 channels): igemm_fwd_kernel
+    p.route = fwd2_takes && (cfg != 3 || n32) && cfg >= 0 && cfg <= 4 ? CN_ROUTE_FWD2 : CN_ROUTE_IGEMM;
+    if (stats && p.route != CN_ROUTE_FWD2) return refuse(CN_EINVAL);      // (a forced tile nobody has: never a kernel without the statistics)
+    p.ret = CN_OK;
+    p.cfg = cfg;
+    p.splits = splits;
+    p.par = par;
+    p.vec = vec;
+    p.family = cfg == 0 ? CN_FAM_FWD_128x128 : cfg == 1 ? CN_FAM_FWD_128x64 : cfg == 3 ? CN_FAM_FWD_128x32 : cfg == 4 ? CN_FAM_FWD_128x96 : CN_FAM_FWD_64x64;
+    if (p.route == CN_ROUTE_FWD2) {
+        p.plain = !par && g.k_d * g.k_h * g.k_w == 1 && g.s_d == 1 && g.s_h == 1 && g.s_w == 1 && g.dl_d == 1 && g.dl_h == 1 &&
+                  g.dl_w == 1 && !g.up && g.p_d == 0 && g.p_h == 0 && g.p_w == 0 && g.out_d == g.in_d && g.out_h == g.in_h &&
+                  g.out_w == g.in_w;
+        cn_fwd2_grid(cfg, M, g.cout, par, splits, p.grid);
+    } else {
+        cn_igemm_fwd_grid(cfg, g, vec, par, splits, p.grid);
+    }
+    return p;
+}
+
+// Performs the plan: the split-K protocol (zero pass or, in deterministic mode, partial slabs + cn_sum_parts; the bias / activation
+// pass behind a split) around ONE launch.  A plan without a launch returns its code before anything is enqueued.
+int run_conv_fwd(const ConvPlan& p, const CnConvGeom& g, const ConvReq& q, const void* x, const float* w, const float* bias,
+                 const float* res, void* y, float slope, float* stats, float stats_slope, hipStream_t s) {
+    if (p.route == CN_ROUTE_UNSUPPORTED) return p.ret;
+    const long M = (long)g.n * g.out_d * g.out_h * g.out_w;
+    const int splits = p.splits;
+    float* parts = nullptr;
+    if (cn_det() && splits > 1) {
+        parts = cn_det_ws(s, (size_t)splits * M * g.cout);
+        if (!parts) return CN_EINVAL;
+    }
+    const int kact = splits > 1 ? CN_ACT_NONE : q.act;
+    if (splits > 1 && !parts) {
+        if (int ez__ = cn_zero_async(y, sizeof(float) * M * g.cout, s)) return ez__;
+    }
+    const long part_stride = parts ? (long)M * g.cout : 0;
+    float* const out = parts ? parts : (float*)y;
+    if (p.family >= 0) cn_prof_begin(s, conv_flops(g), conv_bytes(g, q.x_dt == CN_BF16 ? 2.0 : 4.0, q.y_dt == CN_BF16 ? 2.0 : 4.0), p.family);
+    int e = CN_OK;
+    switch (p.route) {
+        case CN_ROUTE_FWD2: {
+            const double xe = (double)g.n * g.in_d * g.in_h * g.in_w * g.cin, we = (double)g.k_d * g.k_h * g.k_w * g.cin * g.cout;
+            e = cn_fwd2(p.plain ? nullptr : &g, p.cfg, q.bt, (const float*)x, w, bias, out, M, g.cout, g.cin, kact, slope, splits, part_stride,
+                        p.plain ? 0 : p.par, s, res, xe, we, stats, q.stats_mode, stats_slope, p.srows, p.sper);
+            break;
+        }
+        case CN_ROUTE_IGEMM:
+            e = cn_igemm_fwd(p.cfg, g, p.vec, p.par, splits, (const float*)x, w, bias, out, kact, slope, s, q.bt, part_stride, res);
+            break;
+        case CN_ROUTE_THIN_PAR_IGEMM:
+            e = cn_igemm_fwd_thin(g, (const float*)x, w, bias, out, kact, slope, s);
+            break;
+        default:
+            cn_small_conv(p.route, (unsigned)p.grid[0], g, p.vec, p.par, x, q.x_dt, w, bias, y, q.y_dt, kact, slope, s);
+            break;
+    }
+    if (p.family >= 0) cn_prof_end(s);
+    CN_CHECK_ARG(e != CN_EUNSUPPORTED, "convolution plan (route %d, tile %d) refused by its kernel", p.route, p.cfg);      // (a bug: never "nothing launched")
+    if (e != CN_OK) return e;
+    CN_LAUNCH_CHECK();
+    if (parts) e = cn_sum_parts(parts, (float*)y, splits, (long)M * g.cout, 0, 1.f, s);
+    if (e == CN_OK && splits > 1 && q.act != CN_ACT_NONE) e = cn_act_fwd(y, y, (size_t)M * g.cout, q.act, slope, CN_F32, s);
+    return e;
+}
+
+// argument checks, plan, run: the body of every forward / data-gradient entry below
+int conv_fwd(const CnConvGeom* gp, const ConvReq& q, const void* x, const float* w, const float* bias, const float* res, void* y,
+             float slope, float* stats, float stats_slope, void* stream) {
+    if (int e = check_geom(gp)) return e;
+    CN_CHECK_ARG(x && w && y, "NULL tensor");
+    return run_conv_fwd(plan_conv_fwd(*gp, q), *gp, q, x, w, bias, res, y, slope, stats, stats_slope, (hipStream_t)stream);
+}
+
+}  // namespace
+
+extern "C" int cn_conv_fwd(const CnConvGeom* gp, const float* x, const float* w, const float* bias, float* y, int act,
+                           float slope, void* stream) {
+    return conv_fwd(gp, ConvReq{0, bias != nullptr, act, 0, 0, CN_F32, CN_F32}, x, w, bias, nullptr, y, slope, nullptr, 0.f, stream);
+}
+
+extern "C" int cn_conv_fwd_stats(const CnConvGeom* gp, const float* x, const float* w, const float* bias, float* y, int act,
+                                 float slope, float* stats, int stats_mode, float stats_slope, void* stream) {
+    CN_CHECK_ARG(stats && (stats_mode == 1 || stats_mode == 2), "cn_conv_fwd_stats: stats buffer and mode 1 / 2");
+    CN_CHECK_ARG(stats_mode == 1 || act == CN_ACT_NONE, "cn_conv_fwd_stats: mode 2 takes the statistics of the pre-activation output");
+    return conv_fwd(gp, ConvReq{0, bias != nullptr, act, 0, stats_mode, CN_F32, CN_F32}, x, w, bias, nullptr, y, slope, stats, stats_slope, stream);
+}
+
+// y = act(conv(x, w) + bias + res): the residual add of a ResNet block in the convolution's epilogue (real_encoder.py:13 --
+// keras ResNet50's `Add` + `Activation("relu")` behind the block's last 1x1 convolution).  Only unsplit implicit-GEMM launches
+// carry it; CN_EUNSUPPORTED (nothing launched) otherwise.
+extern "C" int cn_conv_fwd_res(const CnConvGeom* gp, const float* x, const float* w, const float* bias, const float* res, float* y,
+                               int act, float slope, void* stream) {
+    CN_CHECK_ARG(res, "cn_conv_fwd_res: res is NULL");
+    return conv_fwd(gp, ConvReq{0, bias != nullptr, act, 1, 0, CN_F32, CN_F32}, x, w, bias, res, y, slope, nullptr, 0.f, stream);
+}
+
+// First / last layers with mixed storage types (the bf16 path keeps 3-channel images in fp32, everything wider in bf16):
+//   * 3x3 / 7x7 convolution of a 3-channel fp32 image written in bf16 (c3_fwd_kernel, c7s2_fwd_kernel), and
+//   * the data gradient of the stride-2 3x3 one INTO the fp32 image from a bf16 output gradient (s2_image_dgrad_kernel, the
+//     geometry cn_conv_dgrad_dt builds),
+// without a conversion pass over the 48 / 64-channel tensor.  Everything else: CN_EUNSUPPORTED, nothing launched.
+extern "C" int cn_conv_fwd_dt(const CnConvGeom* gp, const void* x, int x_dt, const float* w, const float* bias, void* y, int y_dt,
+                              int act, float slope, void* stream) {
+    if (int e = check_geom(gp)) return e;
+    CN_CHECK_ARG(x && w && y, "NULL tensor");
+    if (x_dt == CN_F32 && y_dt == CN_F32) return CN_EUNSUPPORTED;      // (cn_conv_fwd's case)
+    const ConvReq q{0, bias != nullptr, act, 0, 0, x_dt, y_dt};
+    return run_conv_fwd(plan_conv_fwd(*gp, q), *gp, q, x, w, bias, nullptr, y, slope, nullptr, 0.f, (hipStream_t)stream);
+}
+
+extern "C" int cn_conv_dgrad(const CnConvGeom* gp, const float* gy, const float* w_tflip, float* gu, void* stream) {
+    if (int e = check_geom(gp)) return e;
+    CN_CHECK_ARG(gp->dl_d == 1 && gp->dl_h == 1 && gp->dl_w == 1, "dgrad of a dilated-input geometry is not defined here");
+    const CnConvGeom d = dgrad_geom(*gp);
+    return cn_conv_fwd(&d, gy, w_tflip, nullptr, gu, CN_ACT_NONE, 0.f, stream);
+}
+
+extern "C" int cn_conv_dgrad_dt(const CnConvGeom* gp, const void* gy, int gy_dt, const float* w_tflip, void* gu, int gu_dt,
+                                void* stream) {
+    if (int e = check_geom(gp)) return e;
+    if (gp->dl_d != 1 || gp->dl_h != 1 || gp->dl_w != 1) return CN_EUNSUPPORTED;
+    const CnConvGeom d = dgrad_geom(*gp);
+    return cn_conv_fwd_dt(&d, gy, gy_dt, w_tflip, nullptr, gu, gu_dt, CN_ACT_NONE, 0.f, stream);
+}
+
+// Data gradient straight from the ORIGINAL filter w [t][cin][cout] (no cn_conv_weight_tflip copy): CN_EUNSUPPORTED (nothing
+// launched) where the shape does not reach the vectorised implicit-GEMM kernel -- the caller then uses cn_conv_dgrad.
+extern "C" int cn_conv_dgrad_w(const CnConvGeom* gp, const float* gy, const float* w, float* gu, void* stream) {
+    if (int e = check_geom(gp)) return e;
+    if (gp->dl_d != 1 || gp->dl_h != 1 || gp->dl_w != 1) return CN_EUNSUPPORTED;
+    const CnConvGeom d = dgrad_geom(*gp);
+    return conv_fwd(&d, ConvReq{1, 0, CN_ACT_NONE, 0, 0, CN_F32, CN_F32}, gy, w, nullptr, nullptr, gu, 0.f, nullptr, 0.f, stream);
+}
+
+// gu = (data gradient of cn_conv_dgrad_w) + res, res shaped like gu: the SECOND contribution to the gradient of a tensor that
+// feeds a convolution AND a skip connection (a ResNet bottleneck's input, real_encoder.py:13: the gradient of keras' `Add`),
+// added in the data-gradient launch's epilogue instead of by a separate pass.  Stride-1 layers whose launch is an unsplit
+// implicit-GEMM one; CN_EUNSUPPORTED (nothing launched) otherwise -- the caller then adds with a pass of its own.
+extern "C" int cn_conv_dgrad_w_res(const CnConvGeom* gp, const float* gy, const float* w, const float* res, float* gu, void* stream) {
+    if (int e = check_geom(gp)) return e;
+    CN_CHECK_ARG(res, "cn_conv_dgrad_w_res: res is NULL");
+    if (gp->dl_d != 1 || gp->dl_h != 1 || gp->dl_w != 1 || gp->up) return CN_EUNSUPPORTED;
+    if (gp->s_d != 1 || gp->s_h != 1 || gp->s_w != 1) return CN_EUNSUPPORTED;      // (parity-ordered rows: not with a residual)
+    const CnConvGeom d = dgrad_geom(*gp);
+    return conv_fwd(&d, ConvReq{1, 0, CN_ACT_NONE, 1, 0, CN_F32, CN_F32}, gy, w, nullptr, res, gu, 0.f, nullptr, 0.f, stream);
+}
+
+// Diagnostic (include/confignet_hip.h): the launch a request WOULD get -- needs no device, enqueues nothing.
+extern "C" int cn_conv_fwd_plan(const CnConvGeom* gp, int bt, int has_bias, int act, int has_res, int stats_mode, int x_dt, int y_dt,
+                                int out[8]) {
+    if (int e = check_geom(gp)) return e;
+    CN_CHECK_ARG(out, "cn_conv_fwd_plan: out is NULL");
+    const ConvPlan p = plan_conv_fwd(*gp, ConvReq{bt, has_bias, act, has_res, stats_mode, x_dt, y_dt});
+    const int v[8] = {p.route, p.cfg, p.splits, p.par, p.family, p.grid[0], p.grid[1], p.grid[2]};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return p.ret;
+}
+
+extern "C" int cn_conv_wgrad(const CnConvGeom* gp, const float* x, const float* gy, float* gw, int accumulate, void* stream) {
+    if (int e = check_geom(gp)) return e;
+    CN_CHECK_ARG(x && gy && gw, "NULL tensor");
+    const CnConvGeom g = *gp;
+    hipStream_t s = (hipStream_t)stream;
+    if (!accumulate) {
+        const long Ktot = (long)g.k_d * g.k_h * g.k_w * g.cin;
+        if (int ez__ = cn_zero_async(gw, sizeof(float) * Ktot * g.cout, s)) return ez__;
+    }
+    int e = cn_tiny_wgrad(g, x, gy, gw, s);
+    if (e != CN_EUNSUPPORTED) return e;
+    const int cfg = wgrad_tile_cfg(g);
+    cn_prof_begin(s, conv_flops(g), conv_bytes(g), cfg == 3 ? CN_FAM_WGRAD_128x32 : cfg == 4 ? CN_FAM_WGRAD_128x96 : cfg == 0 ? CN_FAM_WGRAD_128x128 : CN_FAM_WGRAD_64x64);
+    e = cn_igemm_wgrad(cfg, g, x, gy, gw, g_tune_wg_blocks, s);
+    cn_prof_end(s);
+    return e;
+}
+
+static bool wgrad2_takes(const CnConvGeom& g) {
+    // Every geometry the LDS-DMA kernel can take (round 6: with the slot layout and the XCD-aware slice plan it is at or ahead of
+    // the round-3 kernel -- split over rows, fp32 atomics -- on every shape of the iteration, profiles/round6_wgrad_shapes.txt).
+    // The round-3 kernel keeps the rest: channel counts that are no multiple of 4, K < 64, > 2 GiB operands.
+    const long Ktot = (long)g.k_d * g.k_h * g.k_w * g.cin;
+    return cn_wgrad2_ok(g) && Ktot >= 64;
+}
+
+// Workspace (bytes) that cn_conv_wgrad_ws needs for this geometry: room for the partial filters of its row splits; 0 = none.
+extern "C" size_t cn_conv_wgrad_workspace_bytes(const CnConvGeom* gp) {
+    if (!gp || check_geom(gp) != CN_OK || !wgrad2_takes(*gp)) return 0;
+    return sizeof(float) * cn_wgrad2_workspace_floats(*gp);
+}
+
+// Filter gradient with a CALLER-OWNED workspace (the caller owns all device memory): LDS-DMA main loop, row splits
+// through partial slabs in `workspace` + one ordered reduction -- no atomics on the tile, bit-reproducible (wgrad2.hip).
+// Geometries the new kernel does not take (channel counts that are no multiple of 4, K < 64, > 2 GiB operands) go to
+// cn_conv_wgrad and need no workspace.
+static int wgrad_ws_impl(const CnConvGeom* gp, const float* x, const float* gy, float* gw, int accumulate, void* workspace,
+                         size_t workspace_bytes, int* parts, void* stream) {
+    if (int e = check_geom(gp)) return e;
+    CN_CHECK_ARG(x && gy && gw, "NULL tensor");
+    if (parts) *parts = 0;
+    if (!wgrad2_takes(*gp)) return cn_conv_wgrad(gp, x, gy, gw, accumulate, stream);
+    const size_t need = sizeof(float) * cn_wgrad2_workspace_floats(*gp);
+    CN_CHECK_ARG(workspace_bytes >= need && (need == 0 || workspace), "cn_conv_wgrad_ws: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    hipStream_t s = (hipStream_t)stream;
+    cn_prof_begin(s, conv_flops(*gp), conv_bytes(*gp), cn_wgrad2_family(*gp));
+    const int e = cn_wgrad2(*gp, x, gy, gw, accumulate, (float*)workspace, s, parts);
+    cn_prof_end(s);
+    return e;
+}
+
+extern "C" int cn_conv_wgrad_ws(const CnConvGeom* gp, const float* x, const float* gy, float* gw, int accumulate, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    return wgrad_ws_impl(gp, x, gy, gw, accumulate, workspace, workspace_bytes, nullptr, stream);
+}
+
+// cn_conv_wgrad_ws that leaves the slabs to the caller (include/confignet_hip.h): *parts = 0 -> gw is complete
+extern "C" int cn_conv_wgrad_ws_slabs(const CnConvGeom* gp, const float* x, const float* gy, float* gw, int accumulate, void* workspace,
+                                      size_t workspace_bytes, int* parts, void* stream) {
+    CN_CHECK_ARG(parts, "cn_conv_wgrad_ws_slabs: parts is NULL");
+    return wgrad_ws_impl(gp, x, gy, gw, accumulate, workspace, workspace_bytes, parts, stream);
+}
+
+// Tuning hook of the forward / data-gradient main loop (include/confignet_hip.h): loop = 1 / 0 forces the LDS-DMA loop on / off for
+// the layers it can take, kb / ns / np its stage depth, stage count and loader waves.  Process-wide; not for production use.
+extern "C" int cn_conv_loop_select(int loop, int kb, int ns, int np) {
+    CN_CHECK_ARG(loop >= -1 && loop <= 1 && (kb == 0 || kb == 16 || kb == 32) && (ns == 0 || ns == 3 || ns == 4) && np >= -1 && np <= 2,
+                 "cn_conv_loop_select: bad argument");
+    g_fwd2_sel = loop;
+    cn_fwd2_tune(kb, ns, np);
+    cn_wgrad2_stages(ns);
+    return CN_OK;
+}
+
+// Tuning hook (scripts/conv_sweep.py): force the tile configuration (0 = 128x128, 1 = 128x64, 2 = 64x64, 3 = 128x32, 4 = 128x96;
+// -1 = heuristic), the split-K factor of cn_conv_fwd / cn_conv_dgrad (0 = heuristic) and the workgroup target of cn_conv_wgrad
+// (0 = default).  Process-wide; not for production use.
+extern "C" int cn_conv_tune(int cfg, int splits, long wg_blocks) {
+    g_tune_cfg = cfg;
+    g_tune_splits = splits;
+    g_tune_wg_blocks = wg_blocks;
+    // the same hook steers cn_conv_wgrad_ws: tile 0 / 4 / 2 / 3 -> 128x128 / 128x96 / 64x64 / 128x32, wg_blocks = workgroup target
+    cn_wgrad2_tune(cfg == 0 ? 0 : cfg == 4 ? 1 : cfg == 2 ? 2 : cfg == 3 ? 3 : cfg == 5 ? 4 : -1, wg_blocks);
+    return CN_OK;
+}

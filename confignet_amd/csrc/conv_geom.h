@@ -1,6 +1,7 @@
-// conv_geom.h -- geometry of the implicit-GEMM convolution family shared by igemm_conv.hip (fp32 MFMA) and igemm_bf16.hip
-// (bf16 MFMA): row decoding, the gather predicate (TF SAME padding, folded x2 upsample, zero-stuffed strided data gradients),
-// parity-class row order, exact algorithmic FLOP count, argument checks.
+// conv_geom.h -- geometry of the implicit-GEMM convolution family shared by igemm_conv.hip, small_conv.hip, fwd2.hip (fp32 MFMA),
+// igemm_bf16.hip (bf16 MFMA) and conv_dispatch.hip (host): row decoding, the gather predicate (TF SAME padding, folded x2 upsample,
+// zero-stuffed strided data gradients), parity-class row order, exact algorithmic FLOP count, argument checks, the geometry of a
+// data gradient and the filter-gradient tile rule.
 #pragma once
 #include "common.h"
 
@@ -121,6 +122,32 @@ inline bool parity_ordered(const CnConvGeom& g) {
     if (g.s_d != 1 || g.s_h != 1 || g.s_w != 1 || g.up) return false;
     if (g.dl_d * g.dl_h * g.dl_w == 1) return false;
     return g.out_d % g.dl_d == 0 && g.out_h % g.dl_h == 0 && g.out_w % g.dl_w == 0;
+}
+
+// The data gradient of convolution g as a convolution of its own: gy (g's output) is the input, a stride becomes a zero-stuffing
+// divisor dl of a stride-1 gather, the padding mirrors (k - 1 - p), the folded upsample is left to the caller (cn_sumpool2): the
+// output has g's UPSAMPLED input extent.  The filter is g's with the taps reversed and the channel axes swapped.
+inline CnConvGeom dgrad_geom(const CnConvGeom& g) {
+    CnConvGeom d = g;
+    d.in_d = g.out_d; d.in_h = g.out_h; d.in_w = g.out_w; d.cin = g.cout;
+    d.out_d = g.in_d << g.up; d.out_h = g.in_h << g.up; d.out_w = g.in_w << g.up;
+    if (g.nd == 2) d.out_d = 1;
+    d.cout = g.cin;
+    d.s_d = d.s_h = d.s_w = 1;
+    d.dl_d = g.s_d; d.dl_h = g.s_h; d.dl_w = g.s_w;
+    d.p_d = g.k_d - 1 - g.p_d; d.p_h = g.k_h - 1 - g.p_h; d.p_w = g.k_w - 1 - g.p_w;
+    d.up = 0;
+    return d;
+}
+
+// Tile of the row-split filter-gradient kernels (fp32 and bf16), in the implicit-GEMM numbering: 3 = 128 (tap, ci) x 32 co,
+// 4 = 128 x 96 (cout 96 / 192 without column padding), 0 = 128 x 128, 2 = 64 x 64
+inline int wgrad_tile_cfg(const CnConvGeom& g) {
+    const long Ktot = (long)g.k_d * g.k_h * g.k_w * g.cin;
+    if (g.cout <= 32) return 3;
+    if (Ktot >= 128 && g.cout % 96 == 0 && g.cout % 128 != 0) return 4;
+    if (Ktot >= 128 && g.cout >= 128) return 0;
+    return 2;
 }
 
 inline int check_geom(const CnConvGeom* g) {

@@ -558,13 +558,16 @@ __global__ __launch_bounds__(256 + 64 * NP) void fwd2_kernel(CnConvGeom g, const
                                                           b_bytes, flip, stats, stats_mode, stats_slope, srows, sper);
 }
 
+// one workgroup per (M tile, N tile): whole rounds of the eight XCDs unless the rows are parity-ordered
+inline unsigned fwd2_grid_x(int ntm, int ntn, int par) { return (unsigned)(par ? ntm * ntn : 8 * cn_cdiv((long)ntm * ntn, 8)); }
+
 template <int WM, int WN, int TM, int TN, bool BT, bool GATHER, int KB, int NS, int NP, bool BF = false>
 int launch2(const CnConvGeom& g, const float* A, const float* B, const float* bias, float* C, long M, int N, int K, int act, float slope,
             int splits, long part_stride, int par, hipStream_t s, const float* res, unsigned a_bytes, unsigned b_bytes, int flip = 1,
             float* stats = nullptr, int stats_mode = 0, float stats_slope = 0.f, int srows = 1, int sper = 1) {
     constexpr int BM = 32 * WM * TM, BN = 32 * WN * TN;
     const int ntm = cn_cdiv(M, BM), ntn = cn_cdiv(N, BN);
-    dim3 grid((unsigned)(par ? ntm * ntn : 8 * cn_cdiv((long)ntm * ntn, 8)), 1, (unsigned)splits);
+    dim3 grid(fwd2_grid_x(ntm, ntn, par), 1, (unsigned)splits);
     hipLaunchKernelGGL((fwd2_kernel<WM, WN, TM, TN, BT, GATHER, KB, NS, NP, BF>), grid, dim3(256 + 64 * NP), 0, s, g, A, B, bias, C, (int)M, N, K, act,
                        slope, ntm, ntn, part_stride, par, res, a_bytes, b_bytes, flip, stats, stats_mode, stats_slope, srows, sper);
     CN_LAUNCH_CHECK();
@@ -581,6 +584,13 @@ void cn_fwd2_tune(int kb, int ns, int np) {
     g_fwd2_kb = kb;
     g_fwd2_ns = ns;
     g_fwd2_np = np;
+}
+
+void cn_fwd2_grid(int cfg, long M, int N, int par, int splits, int grid[3]) {
+    const int bm = cfg == 2 ? 64 : 128, bn = cfg == 0 ? 128 : cfg == 4 ? 96 : cfg == 3 ? 32 : 64;      // cn_fwd2's tiles
+    grid[0] = (int)fwd2_grid_x(cn_cdiv(M, bm), cn_cdiv(N, bn), par);
+    grid[1] = 1;
+    grid[2] = splits;
 }
 
 // The contract stated in common.h: tile cfg 0 / 1 / 2 / 4, bt = B is the original filter [N][K] (data gradient), split-K

@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_kernel(CnConvGeom g, const bf1
 // filter gradient:  GW[(t,ci), co] += sum_m X[src(m,t), ci] * GY[m, co]   (fp32 output, split over m, fp32 atomics)
 // ---------------------------------------------------------------------------------------------
 // Filter-gradient launches: (tap-channel tile, cout tile, row slice) of this workgroup.  tiles_x == 0: the 3-D grid as it is.  Else
-// the XCD-aware 1-D order (the fp32 kernels' rule, igemm_conv.hip): workgroup id runs on XCD id % 8, and every tile of ONE row
+// the XCD-aware 1-D order (the fp32 kernels' rule, igemm_conv.hip: igemm_wgrad_kernel): workgroup id runs on XCD id % 8, and every tile of ONE row
 // slice goes to the same XCD -- the slice of X and GY they all read enters that XCD's L2 once.  false: a padding workgroup.
 __device__ __forceinline__ bool wgrad_tile_of_workgroup(int tiles_x, int tiles_y, int nsplits, int& bx, int& by, int& bz) {
     bx = blockIdx.x; by = blockIdx.y; bz = blockIdx.z;
@@ -516,15 +516,7 @@ extern "C" int cn_conv_dgrad_bf16(const CnConvGeom* gp, const uint16_t* gy, cons
     CN_CHECK_ARG(gy && wd && gu, "NULL tensor");
     CN_CHECK_ARG(gp->dl_d == 1 && gp->dl_h == 1 && gp->dl_w == 1, "dgrad of a dilated-input geometry is not defined here");
     CN_CHECK_ARG((((uintptr_t)gy | (uintptr_t)wd | (uintptr_t)gu) & 15) == 0, "bf16 convolution needs 16-byte aligned tensors");
-    CnConvGeom d = *gp;
-    d.in_d = gp->out_d; d.in_h = gp->out_h; d.in_w = gp->out_w; d.cin = gp->cout;
-    d.out_d = gp->in_d << gp->up; d.out_h = gp->in_h << gp->up; d.out_w = gp->in_w << gp->up;
-    if (gp->nd == 2) d.out_d = 1;
-    d.cout = gp->cin;
-    d.s_d = d.s_h = d.s_w = 1;
-    d.dl_d = gp->s_d; d.dl_h = gp->s_h; d.dl_w = gp->s_w;
-    d.p_d = gp->k_d - 1 - gp->p_d; d.p_h = gp->k_h - 1 - gp->p_h; d.p_w = gp->k_w - 1 - gp->p_w;
-    d.up = 0;
+    const CnConvGeom d = dgrad_geom(*gp);
     return conv_bf16(d, 1, gy, wd, nullptr, gu, CN_ACT_NONE, 0.f, (hipStream_t)stream);
 }
 
@@ -542,10 +534,12 @@ extern "C" int cn_conv_wgrad_bf16(const CnConvGeom* gp, const uint16_t* x, const
     }
     cn_prof_begin(s, conv_flops(g), conv_bytes(g, 2.0, 2.0, 4.0), CN_FAM_BF16_WGRAD);
     int e;
-    if (g.cout <= 32) e = launch_bf16_wgrad<4, 1, 1, 1>(g, x, gy, gw, s);                                     // 128 (tap,ci) x 32 co
-    else if (Ktot >= 128 && g.cout % 96 == 0 && g.cout % 128 != 0) e = launch_bf16_wgrad<4, 1, 1, 3>(g, x, gy, gw, s);   // 128 x 96
-    else if (Ktot >= 128 && g.cout >= 128) e = launch_bf16_wgrad<2, 2, 2, 2>(g, x, gy, gw, s);                // 128 x 128
-    else e = launch_bf16_wgrad<2, 2, 1, 1>(g, x, gy, gw, s);                                                  // 64 x 64
+    switch (wgrad_tile_cfg(g)) {
+        case 3: e = launch_bf16_wgrad<4, 1, 1, 1>(g, x, gy, gw, s); break;       // 128 (tap,ci) x 32 co
+        case 4: e = launch_bf16_wgrad<4, 1, 1, 3>(g, x, gy, gw, s); break;       // 128 x 96
+        case 0: e = launch_bf16_wgrad<2, 2, 2, 2>(g, x, gy, gw, s); break;       // 128 x 128
+        default: e = launch_bf16_wgrad<2, 2, 1, 1>(g, x, gy, gw, s); break;      // 64 x 64
+    }
     cn_prof_end(s);
     return e;
 }

@@ -202,6 +202,13 @@ int cn_conv_fwd_wino4(int n, int h, int w, int cin, int cout, const float* x, co
 /* Tuning hook: force the tile configuration (0 = 128x128, 1 = 128x64, 2 = 64x64, 3 = 128x32, 4 = 128x96; -1 = heuristic), the
  * split-K factor of cn_conv_fwd / cn_conv_dgrad (0 = heuristic) and the workgroup target of cn_conv_wgrad (0 = default). */
 int cn_conv_tune(int cfg, int splits, long wg_blocks);
+/* Diagnostic: the launch cn_conv_fwd / _res / _stats / _dt (g = the convolution) or cn_conv_dgrad* (g = the data-gradient geometry the
+ * call derives; bt = 1 for cn_conv_dgrad_w*) WOULD get for this request, decided exactly as the call decides it, without a device and
+ * without enqueuing anything.  out = {route, tile cfg, K splits, parity-ordered rows, profile family (-1: none), grid x, y, z};
+ * route: 0 up2k4-rgb, 1 / 2 stride-2 / stride-1 image data gradient, 3 thin parity-ordered implicit GEMM, 4 thin cooperative, 5 thin,
+ * 6 / 7 3x3 / 7x7-stride-2 first layer, 8 LDS-DMA loop, 9 implicit-GEMM loop, 10 nothing is launched.  Returns what the call would
+ * return before launching: CN_OK, or the code (CN_EUNSUPPORTED / CN_EINVAL) of a request that launches nothing. */
+int cn_conv_fwd_plan(const CnConvGeom* g, int bt, int has_bias, int act, int has_res, int stats_mode, int x_dt, int y_dt, int out[8]);
 /* Tuning hook of the forward / data-gradient main loop (csrc/fwd2.hip, the LDS-DMA loop): loop = 1 / 0 forces it on / off for the
  * layers it can take, -1 = the built-in choice; kb = 16 / 32 its stage depth (0 = default), ns = 3 / 4 its stage count (0 = default),
  * np = 0 / 1 / 2 its loader waves (waves that only issue the LDS-DMA; -1 = default). */

@@ -89,9 +89,9 @@ def test_the_image_kernels_issue_all_their_staging_loads_before_the_first_wait(t
         pytest.skip("no hipcc")
     csrc = os.path.join(ROOT, "confignet_amd", "csrc")
     subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-save-temps", "-c",
-                    os.path.join(csrc, "igemm_conv.hip"), "-I" + csrc, "-I" + os.path.join(ROOT, "include"), "-o", "igemm_conv.o"],
+                    os.path.join(csrc, "small_conv.hip"), "-I" + csrc, "-I" + os.path.join(ROOT, "include"), "-o", "small_conv.o"],
                    cwd=tmp_path, check=True, capture_output=True)
-    lines = open(os.path.join(tmp_path, "igemm_conv-hip-amdgcn-amd-amdhsa-gfx950.s")).read().split("\n")
+    lines = open(os.path.join(tmp_path, "small_conv-hip-amdgcn-amd-amdhsa-gfx950.s")).read().split("\n")
     starts = [i for i, l in enumerate(lines) if re.match(r"^_Z\S*(c3_fwd_kernel|c7s2_fwd_kernel)\S*:", l)]
     assert len(starts) >= 12                                        # 4 + 4 instances of the 3x3 kernel, 2 + 2 of the 7x7 one
     for i in starts:

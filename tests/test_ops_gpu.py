@@ -141,6 +141,69 @@ def test_conv_fwd_dgrad_wgrad(case):
     close(gw, wr.grad, tol=5e-4, what="wgrad")
 
 
+PLANNED_LAUNCH_CASES = [
+    # (x shape, kernel, cout, stride, up, explicit_pad, data gradient?): one per route of csrc/conv_dispatch.hip's plan
+    ((1, 32, 32, 3), (3, 3), 48, 2, 0, None, False),          # 3x3 first layer
+    ((1, 64, 64, 3), (7, 7), 64, 2, 0, 3, False),             # 7x7 stride-2 first layer
+    ((1, 16, 16, 32), (4, 4), 3, 1, 1, None, False),          # map_final
+    ((1, 32, 32, 3), (3, 3), 48, 2, 0, None, True),           # data gradient of the first case, into the image
+    ((1, 16, 16, 8), (3, 3), 1, 1, 0, None, False),           # thin output: a launch without a profile bracket
+    ((2, 16, 16, 64), (3, 3), 128, 1, 0, None, False),        # LDS-DMA loop
+    ((2, 128, 128, 48), (3, 3), 96, 1, 0, None, False),       # ... 96 output channels
+    ((1, 32, 32, 32), (3, 3), 32, 1, 0, None, False),         # ... 32 output channels
+    ((1, 16, 16, 24), (3, 3), 64, 1, 0, None, False),         # cin % 16 != 0: the register-staged loop, scalar gather
+    ((1, 8, 8, 512), (3, 3), 512, 1, 0, None, False),         # 16 K slices
+]
+
+
+@pytest.mark.parametrize("case", PLANNED_LAUNCH_CASES, ids=[str(i) for i in range(len(PLANNED_LAUNCH_CASES))])
+def test_the_launch_is_the_one_the_plan_names(case):
+    """cn_conv_fwd_plan says which launch a request gets; with profiling on, cn_conv_fwd / cn_conv_dgrad must then show exactly one
+    launch, in the family the plan names (none where the plan's launch has no profile bracket) -- and compute the convolution."""
+    from confignet_amd import ops
+    from confignet_amd._lib import lib
+    xs, k, cout, stride, up, epad, dgrad = case
+    rng = np.random.default_rng(7 + cout + xs[-1])
+    cin = xs[-1]
+    x = rng.normal(size=xs)
+    w = rng.normal(size=(*k, cin, cout)) / math.sqrt(np.prod(k) * cin)
+    b = rng.normal(size=cout)
+    g = ops.ConvSpec(k, stride=stride, up=up, explicit_pad=epad).geom(xs, cout)
+    out = (ctypes.c_int * 8)()
+    if dgrad:
+        d = ops._copy_geom(g, in_d=g.out_d, in_h=g.out_h, in_w=g.out_w, cin=g.cout, out_d=1, out_h=g.in_h, out_w=g.in_w, cout=g.cin,
+                           s_h=1, s_w=1, dl_h=g.s_h, dl_w=g.s_w, p_h=g.k_h - 1 - g.p_h, p_w=g.k_w - 1 - g.p_w)
+        ops.check(lib.cn_conv_fwd_plan(ctypes.byref(d), 0, 0, 0, 0, 0, 0, 0, ctypes.byref(out)), "cn_conv_fwd_plan")
+        xr = t64(x).requires_grad_(True)
+        yr = _oracle_conv(xr, t64(w), None, stride, 0, epad, 0, 0.0)
+        gy = rng.normal(size=tuple(yr.shape))
+        (yr * t64(gy)).sum().backward()
+        ref = xr.grad
+        gyd, wt = dev(gy), ops.weight_tflip(dev(w))
+        y = torch.empty(xs, device="cuda", dtype=torch.float32)
+        call = lambda: lib.cn_conv_dgrad(ctypes.byref(g), ops._ptr(gyd), ops._ptr(wt), ops._ptr(y), ops._stream())
+    else:
+        ops.check(lib.cn_conv_fwd_plan(ctypes.byref(g), 0, 1, 1, 0, 0, 0, 0, ctypes.byref(out)), "cn_conv_fwd_plan")
+        ref = _oracle_conv(t64(x), t64(w), t64(b), stride, up, epad, 1, 0.3)
+        xd, wd, bd = dev(x), dev(w), dev(b)
+        y = torch.empty(ops.geom_out_shape(g), device="cuda", dtype=torch.float32)
+        call = lambda: lib.cn_conv_fwd(ctypes.byref(g), ops._ptr(xd), ops._ptr(wd), ops._ptr(bd), ops._ptr(y), 1, 0.3, ops._stream())
+    family = out[4]
+    torch.cuda.synchronize()
+    ops.prof_enable(True)
+    try:
+        ops.prof_reset()
+        ops.check(call(), "convolution")
+        torch.cuda.synchronize()
+        shown = ops.prof_collect_by_family()
+    finally:
+        ops.prof_enable(False)
+    print("plan", list(out), "profile", {name: v["launches"] for name, v in shown.items()})
+    want = {} if family < 0 else {ops.PROF_FAMILIES[family]: 1}
+    assert {name: v["launches"] for name, v in shown.items()} == want, (list(out), shown)
+    close(y, ref, what="planned launch")
+
+
 # The layer shapes of the 256x256, batch-16 iteration (BASELINE.json configs[1]): the tile / split-K / XCD-order / Winograd
 # code paths are selected BY SIZE, so the small cases above never reach them.  Each layer is compared with the float64
 # oracle on the FULL tensors (forward, data gradient, filter gradient: seconds per layer on the host), and -- second line of
