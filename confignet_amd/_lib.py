@@ -99,7 +99,7 @@ SIGNATURES = {
     "cn_nc_reduce4": [_p, _p, _i, _i, _i, _f, _i, _i, _p],
     "cn_nc_reduce": [_p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _p],
     "cn_nc_lin2": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p],
-    "cn_norm_coef_fwd": [_i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _p],
+    "cn_norm_coef_fwd": [_i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _p, _i, _p],
     "cn_norm_coef_bwd": [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _p],
     "cn_dual_tail_coef_fwd": [_p] * 13 + [_i, _i, _i, _f, _i, _i, _p],
     "cn_dual_tail_coef_bwd": [_p] * 13 + [ctypes.POINTER(ctypes.c_void_p), _i, _i, _i, _f, _i, _i, _p],

@@ -64,10 +64,12 @@ __global__ __launch_bounds__(256) void nc_reduce_kernel(const T* __restrict__ x1
                 for (int u = 0; u < 4; ++u) {
                     float4 a = va[u], b = vb[u];
                     if (flags & 1) a = lrelu4(a, slope);
-                    if (x2) { if (flags & 2) b = lrelu4(b, slope); }
-                    if (dact_on) {
+                    if (dact_on) {                 // (the derivative from x2 itself, before f2: f2 belongs to the second sum only)
                         a.x *= act_deriv(b.x, dact, slope); a.y *= act_deriv(b.y, dact, slope);
                         a.z *= act_deriv(b.z, dact, slope); a.w *= act_deriv(b.w, dact, slope);
+                    }
+                    if (x2) { if (flags & 2) b = lrelu4(b, slope); }
+                    if (dact_on) {
                         if (dact_out) st4<T>(dact_out + base + (long)(s + u * TY) * C, a);
                         if (scaled_out) {
                             const float4 k4 = *reinterpret_cast<const float4*>(coef + (long)cg * V);
@@ -89,12 +91,14 @@ __global__ __launch_bounds__(256) void nc_reduce_kernel(const T* __restrict__ x1
                 a[0] = va.x; a[1 % V] = va.y; a[2 % V] = va.z; a[3 % V] = va.w;
                 if (x2) {
                     float4 vb = ld4<T>(x2 + base2 + (long)s * C);
+                    if (dact_on) {
+                        a[0] *= act_deriv(vb.x, dact, slope); a[1 % V] *= act_deriv(vb.y, dact, slope);
+                        a[2 % V] *= act_deriv(vb.z, dact, slope); a[3 % V] *= act_deriv(vb.w, dact, slope);
+                    }
                     if (flags & 2) vb = lrelu4(vb, slope);
                     b[0] = vb.x; b[1 % V] = vb.y; b[2 % V] = vb.z; b[3 % V] = vb.w;
                 }
                 if (dact_on) {
-#pragma unroll
-                    for (int e = 0; e < V; ++e) a[e] *= act_deriv(b[e], dact, slope);
                     if (dact_out) st4<T>(dact_out + base + (long)s * C, make_float4(a[0], a[1 % V], a[2 % V], a[3 % V]));
                     if (scaled_out) {
                         const float4 k4 = *reinterpret_cast<const float4*>(coef + (long)cg * V);
@@ -110,10 +114,10 @@ __global__ __launch_bounds__(256) void nc_reduce_kernel(const T* __restrict__ x1
                 if (flags & 1) a[0] = lrelu(a[0], slope);
                 if (x2) {
                     b[0] = ldf<T>(x2 + base2 + (long)s * C);
+                    if (dact_on) a[0] *= act_deriv(b[0], dact, slope);
                     if (flags & 2) b[0] = lrelu(b[0], slope);
                 }
                 if (dact_on) {
-                    a[0] *= act_deriv(b[0], dact, slope);
                     if (dact_out) stf<T>(dact_out + base + (long)s * C, a[0]);
                     if (scaled_out) stf<T>(scaled_out + base + (long)s * C, a[0] * coef[cg]);
                     if (x3) b[0] = ldf<T>(x3 + base + (long)s * C);
@@ -471,9 +475,10 @@ __global__ __launch_bounds__(256) void norm_apply_rows_kernel(NormApplyArgs A, c
         k2[e] = 0.f;
         if (A.dir == 0) {
             const float mu = A.s1[i] * A.invS;
-            const float var = fmaxf(A.s2[i] * A.invS - mu * mu, 0.f);
+            float var = fmaxf(A.s2[i] * A.invS - mu * mu, 0.f);
             float rr, a;
             if (A.mode == 0) {
+                if (cn_adain_refine(mu, var, A.eps)) var = cn_var_two_pass<T>(x1 + (long)n * (G / CG) * C + c, G / CG, C, mu, A.invS);
                 rr = rsqrtf(var + A.eps);
                 a = rr * (A.p1[(long)n * 2 * C + c] + 1.f);
                 kb[e] = A.p1[(long)n * 2 * C + C + c] - mu * a;

@@ -5,17 +5,19 @@
 
 namespace {
 
+template <typename T>
 __global__ void norm_coef_fwd_kernel(int mode, const float* __restrict__ s1, const float* __restrict__ s2,
                                      const float* __restrict__ p1, const float* __restrict__ p2, float* __restrict__ A,
                                      float* __restrict__ B, float* __restrict__ sm, float* __restrict__ sr, int N, int C,
-                                     float invS, float eps) {
+                                     float invS, float eps, const T* __restrict__ x, int S) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N * C) return;
     const int n = i / C, c = i - n * C;
     const float mu = s1[i] * invS;
-    const float var = fmaxf(s2[i] * invS - mu * mu, 0.f);
+    float var = fmaxf(s2[i] * invS - mu * mu, 0.f);
     sm[i] = mu;
     if (mode == 0) {
+        if (x && cn_adain_refine(mu, var, eps)) var = cn_var_two_pass<T>(x + (long)n * S * C + c, S, C, mu, invS);
         const float r = rsqrtf(var + eps);
         const float a = r * (p1[n * 2 * C + c] + 1.f);
         sr[i] = r;
@@ -93,12 +95,15 @@ __global__ void norm_coef_bwd_kernel(int mode, const float* __restrict__ t1, con
 }  // namespace
 
 extern "C" int cn_norm_coef_fwd(int mode, const float* s1, const float* s2, const float* p1, const float* p2, float* A,
-                                float* B, float* save_mean, float* save_r, int n, int c, int S, float eps, void* stream) {
+                                float* B, float* save_mean, float* save_r, int n, int c, int S, float eps, const void* x, int dt,
+                                void* stream) {
     CN_CHECK_ARG(mode >= 0 && mode <= 2 && s1 && s2 && A && save_mean && save_r && n > 0 && c > 0 && S > 0, "norm_coef_fwd: bad args");
     CN_CHECK_ARG(mode == 2 || (p1 && B), "norm_coef_fwd: missing parameter tensor");
     CN_CHECK_ARG(mode != 1 || p2, "norm_coef_fwd: instance norm needs beta");
-    hipLaunchKernelGGL(norm_coef_fwd_kernel, dim3(cn_cdiv((long)n * c, 256)), dim3(256), 0, (hipStream_t)stream, mode, s1, s2, p1,
-                       p2, A, B, save_mean, save_r, n, c, 1.f / (float)S, eps);
+    CN_CHECK_ARG(!x || dt == CN_F32 || dt == CN_BF16, "norm_coef_fwd: bad dtype code %d", dt);
+    // x (mode 0, may be NULL): the normalised tensor itself, read only by channels whose one-pass variance cannot be trusted (typed.h)
+    CN_DISPATCH_DT(x ? dt : CN_F32, hipLaunchKernelGGL((norm_coef_fwd_kernel<T>), dim3(cn_cdiv((long)n * c, 256)), dim3(256), 0, (hipStream_t)stream,
+                                                       mode, s1, s2, p1, p2, A, B, save_mean, save_r, n, c, 1.f / (float)S, eps, (const T*)x, S));
     CN_LAUNCH_CHECK();
     return CN_OK;
 }
@@ -221,13 +226,29 @@ __global__ void dual_coef_bwd_kernel(const float* __restrict__ H1, const float* 
     }
 }
 
+// V consecutive channels of one position: a 16-byte (fp32) access for V = 4, one element for V = 1 (c % 4 != 0)
+template <int V, typename T>
+__device__ __forceinline__ void ldv(const T* __restrict__ p, float (&o)[V]) {
+    if constexpr (V == 4) {
+        const float4 t = ld4<T>(p);
+        o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
+    } else {
+        o[0] = ldf<T>(p);
+    }
+}
+template <int V, typename T>
+__device__ __forceinline__ void stv(T* __restrict__ p, const float (&v)[V]) {
+    if constexpr (V == 4) st4<T>(p, make_float4(v[0], v[1], v[2], v[3]));
+    else stf<T>(p, v[0]);
+}
+
 // g_x = lrelu'(x) (kh*h + kt*ta + ka*lrelu(x) + kc) + et*tx + ex*x + e0 ; any of the two groups may be absent
-template <typename T>
+template <int V, typename T>
 __global__ void dual_gx_kernel(const T* __restrict__ h, const T* __restrict__ ta, const T* __restrict__ tx,
                                const T* __restrict__ x, const float* __restrict__ kh, const float* __restrict__ kt,
                                const float* __restrict__ ka, const float* __restrict__ kc, const float* __restrict__ et,
                                const float* __restrict__ ex, const float* __restrict__ e0, T* __restrict__ out,
-                               long total4, int S, int C, float slope, int nrep, const float* __restrict__ K1 = nullptr,
+                               long totalV, int S, int C, float slope, int nrep, const float* __restrict__ K1 = nullptr,
                                const float* __restrict__ K2 = nullptr, const float* __restrict__ K0 = nullptr,
                                const float* __restrict__ D2 = nullptr, const float* __restrict__ D0 = nullptr,
                                T* __restrict__ out_tx = nullptr, int ta_is_tx = 0) {
@@ -235,60 +256,60 @@ __global__ void dual_gx_kernel(const T* __restrict__ h, const T* __restrict__ ta
     // out_tx (round 6, cn_dual_tail_gx_tx): the gradient w.r.t. the stacked tangent input from the SAME pass over h and x --
     // rows [0, N): D2 x + D0 (the head that left through the style statistics), rows [(1 + j) N, (2 + j) N): lrelu'(x) (K1 h_j + K2
     // lrelu(x) + K0) -- what two cn_nc_lin2 launches (one more read of h) computed before
-    // total4 = N*S*C/4 elements of x / out; h, ta and their coefficients hold nrep*N samples (the heads of a batched tangent
-    // pass that share this primal activation): their contributions are summed here, in head order
-    const int C4 = C / 4;
-    const long NC = (total4 / S / C4) * (long)C;         // N * C: coefficient rows per head
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (long)gridDim.x * blockDim.x) {
-        const int cg = (int)(i % C4);
-        const int n = (int)((i / C4) / S);
-        const long ci = (long)n * C + (long)cg * 4;
-        const float4 xv = ld4<T>(x + 4 * i);
-        const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
-        float r[4] = {0.f, 0.f, 0.f, 0.f};
+    // totalV = N*S*C/V groups of V channels of x / out (V = 4 where c % 4 == 0, else 1); h, ta and their coefficients hold nrep*N
+    // samples (the heads of a batched tangent pass that share this primal activation): their contributions are summed here, in head order
+    const int CV = C / V;
+    const long NC = (totalV / S / CV) * (long)C;         // N * C: coefficient rows per head
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < totalV; i += (long)gridDim.x * blockDim.x) {
+        const int cg = (int)(i % CV);
+        const int n = (int)((i / CV) / S);
+        const long ci = (long)n * C + (long)cg * V;
+        float xs[V], r[V];
+        ldv<V, T>(x + V * i, xs);
+#pragma unroll
+        for (int e = 0; e < V; ++e) r[e] = 0.f;
         if (kh) {
             for (int j = 0; j < nrep; ++j) {
-                const float4 hv = ld4<T>(h + 4 * (i + j * total4));
-                const float4 tv = ld4<T>(ta + 4 * (i + j * total4));
-                const float hs[4] = {hv.x, hv.y, hv.z, hv.w};
-                float ts[4] = {tv.x, tv.y, tv.z, tv.w};
+                float hs[V], ts[V];
+                ldv<V, T>(h + V * (i + j * totalV), hs);
+                ldv<V, T>(ta + V * (i + j * totalV), ts);
                 if (ta_is_tx) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) ts[e] *= xs[e] > 0.f ? 1.f : slope;
+                    for (int e = 0; e < V; ++e) ts[e] *= xs[e] > 0.f ? 1.f : slope;
                 }
                 const long cj = ci + j * NC;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
+                for (int e = 0; e < V; ++e) {
                     const float mk = xs[e] > 0.f ? 1.f : slope;
                     r[e] += mk * (kh[cj + e] * hs[e] + kt[cj + e] * ts[e] + ka[cj + e] * xs[e] * mk + kc[cj + e]);
                 }
                 if (out_tx) {
-                    float w[4];
+                    float w[V];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
+                    for (int e = 0; e < V; ++e) {
                         // (the operation order of nc_lin2_rows_kernel with flags 2 | 4: bias, + a1 x1, + a2 lrelu(x2), times lrelu'(x2))
                         float v = K0[cj + e];
                         v += K1[cj + e] * hs[e];
                         v += K2[cj + e] * (xs[e] > 0.f ? xs[e] : xs[e] * slope);
                         w[e] = v * (xs[e] > 0.f ? 1.f : slope);
                     }
-                    st4<T>(out_tx + 4 * (i + (long)(j + 1) * total4), make_float4(w[0], w[1], w[2], w[3]));
+                    stv<V, T>(out_tx + V * (i + (long)(j + 1) * totalV), w);
                 }
             }
         }
         if (et) {
-            const float4 tv = ld4<T>(tx + 4 * i);
-            const float ts[4] = {tv.x, tv.y, tv.z, tv.w};
+            float ts[V];
+            ldv<V, T>(tx + V * i, ts);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) r[e] += et[ci + e] * ts[e] + ex[ci + e] * xs[e] + e0[ci + e];
+            for (int e = 0; e < V; ++e) r[e] += et[ci + e] * ts[e] + ex[ci + e] * xs[e] + e0[ci + e];
         }
         if (out_tx) {
-            float w[4];
+            float w[V];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) w[e] = D0[ci + e] + D2[ci + e] * xs[e];
-            st4<T>(out_tx + 4 * i, make_float4(w[0], w[1], w[2], w[3]));
+            for (int e = 0; e < V; ++e) w[e] = D0[ci + e] + D2[ci + e] * xs[e];
+            stv<V, T>(out_tx + V * i, w);
         }
-        st4<T>(out + 4 * i, make_float4(r[0], r[1], r[2], r[3]));
+        stv<V, T>(out + V * i, r);
     }
 }
 
@@ -333,14 +354,19 @@ extern "C" int cn_dual_tail_coef_bwd(const float* H1, const float* H2p, const fl
 extern "C" int cn_dual_tail_gx(const void* h, const void* ta, const void* tx, const void* x, const float* kh,
                                const float* kt, const float* ka, const float* kc, const float* et, const float* ex,
                                const float* e0, void* out, int n, int s, int c, float slope, int nrep, int dt, void* stream) {
-    CN_CHECK_ARG(x && out && n > 0 && s > 0 && c > 0 && c % 4 == 0 && (kh || et) && nrep >= 1 && (dt == CN_F32 || dt == CN_BF16), "dual_tail_gx: bad args");
+    CN_CHECK_ARG(x && out && n > 0 && s > 0 && c > 0 && (kh || et) && nrep >= 1 && (dt == CN_F32 || dt == CN_BF16), "dual_tail_gx: bad args");
     CN_CHECK_ARG(!kh || (h && ta && kt && ka && kc), "dual_tail_gx: missing instance-norm tensors");
     CN_CHECK_ARG(!et || (tx && ex && e0), "dual_tail_gx: missing style tensors");
-    const long total4 = (long)n * s * (c / 4);
-    long blocks = (total4 + 255) / 256;
+    const int V = (c % 4 == 0) ? 4 : 1;                 // (c % 4 != 0: one channel per thread, as the other kernels of the family)
+    const long totalV = (long)n * s * (c / V);
+    long blocks = (totalV + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    CN_DISPATCH_DT(dt, hipLaunchKernelGGL((dual_gx_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)h,
-                                          (const T*)ta, (const T*)tx, (const T*)x, kh, kt, ka, kc, et, ex, e0, (T*)out, total4, s, c, slope, nrep));
+    CN_DISPATCH_DT(dt, {
+        if (V == 4) hipLaunchKernelGGL((dual_gx_kernel<4, T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)h,
+                                       (const T*)ta, (const T*)tx, (const T*)x, kh, kt, ka, kc, et, ex, e0, (T*)out, totalV, s, c, slope, nrep);
+        else hipLaunchKernelGGL((dual_gx_kernel<1, T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)h,
+                                (const T*)ta, (const T*)tx, (const T*)x, kh, kt, ka, kc, et, ex, e0, (T*)out, totalV, s, c, slope, nrep);
+    });
     CN_LAUNCH_CHECK();
     return CN_OK;
 }
@@ -359,7 +385,7 @@ extern "C" int cn_dual_tail_gx_tx(const void* h, const void* ta, const void* tx,
     const long total4 = (long)n * s * (c / 4);
     long blocks = (total4 + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    CN_DISPATCH_DT(dt, hipLaunchKernelGGL((dual_gx_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)h,
+    CN_DISPATCH_DT(dt, hipLaunchKernelGGL((dual_gx_kernel<4, T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)h,
                                           (const T*)ta, (const T*)tx, (const T*)x, kh, kt, ka, kc, et, ex, e0, (T*)out, total4, s, c, slope, nrep,
                                           K1, K2, K0, D2, D0, (T*)out_tx, ta_is_tx));
     CN_LAUNCH_CHECK();

@@ -40,6 +40,32 @@ template <> __device__ __forceinline__ void st4<bf16_t>(bf16_t* p, float4 v) {
     *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
 }
 
+// AdaIn's variance where the one-pass form fails.  s2 / S - mu^2 from fp32 sums carries an absolute error of ~2e-6 mu^2 (measured:
+// 2.2e-5 at mu = 3.7, S = 4096) whatever produced the sums (cn_nc_reduce or a convolution epilogue); AdaIn adds eps under the
+// root, so that error matters once it is no longer small against var + eps -- an almost constant channel with a large mean.
+// cn_adain_refine() says when: mu^2 > 1000 (var + eps), a mean above ~31 standard deviations; below it the residue stays under
+// 2e-3 of var + eps, i.e. 1e-3 of r = rsqrt(var + eps).  cn_var_two_pass() then takes mean((x - mu)^2) of one (sample, channel)
+// again from the tensor, one thread, fixed order: both users (norm_coef_fwd_kernel, norm_apply_rows_kernel) get the same bits.
+// A thread that meets the condition walks S strided elements.
+__device__ __forceinline__ bool cn_adain_refine(float mu, float var, float eps) { return mu * mu > 1000.f * (var + eps); }
+template <typename T>
+__device__ __forceinline__ float cn_var_two_pass(const T* __restrict__ x, int S, int C, float mu, float invS) {
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    int s = 0;
+    for (; s + 3 < S; s += 4) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float d = ldf<T>(x + (long)(s + u) * C) - mu;
+            acc[u] = fmaf(d, d, acc[u]);
+        }
+    }
+    for (; s < S; ++s) {
+        const float d = ldf<T>(x + (long)s * C) - mu;
+        acc[0] = fmaf(d, d, acc[0]);
+    }
+    return ((acc[0] + acc[1]) + (acc[2] + acc[3])) * invS;
+}
+
 // runtime dispatch on the dtype code of the C ABI
 #define CN_DISPATCH_DT(dt, ...)                                     \
     do {                                                            \

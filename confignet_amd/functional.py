@@ -498,7 +498,7 @@ class AdaInFn(Function):
             y, mean, r = fused
             ctx.save_for_backward(x, sb, mean, r)
             return y
-        a, b, mean, r = ops.norm_coef_fwd(ops.NORM_ADAIN, s1, s2, sb, None, sp, 1e-3)
+        a, b, mean, r = ops.norm_coef_fwd(ops.NORM_ADAIN, s1, s2, sb, None, sp, 1e-3, x)
         ctx.save_for_backward(x, sb, mean, r)
         return ops.nc_lin2(tuple(x.shape), x, a, b=b)
 

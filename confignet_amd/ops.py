@@ -937,14 +937,15 @@ def nc_lin2(shape, x1=None, a1=None, x2=None, a2=None, b=None, flags=0, slope=0.
 NORM_ADAIN, NORM_INSTANCE, NORM_STYLE = 0, 1, 2
 
 
-def norm_coef_fwd(mode, s1, s2, p1, p2, spatial, eps):
+def norm_coef_fwd(mode, s1, s2, p1, p2, spatial, eps, x=None):
+    """x (NORM_ADAIN): the normalised tensor, read by channels whose one-pass variance cannot be trusted (cn_norm_coef_fwd)."""
     n, c = s1.shape
     A = torch.empty((n, 2 * c) if mode == NORM_STYLE else (n, c), device=s1.device, dtype=torch.float32)
     B = torch.empty((n, c), device=s1.device, dtype=torch.float32) if mode != NORM_STYLE else None
     mean = torch.empty((n, c), device=s1.device, dtype=torch.float32)
     r = torch.empty((n, c), device=s1.device, dtype=torch.float32)
     check(lib.cn_norm_coef_fwd(mode, _ptr(s1), _ptr(s2), _ptr(p1), _ptr(p2), _ptr(A), _ptr(B), _ptr(mean), _ptr(r),
-                               n, c, spatial, eps, _stream()), "cn_norm_coef_fwd")
+                               n, c, spatial, eps, _ptr(x), CN_F32 if x is None else _dt(x), _stream()), "cn_norm_coef_fwd")
     return A, B, mean, r
 
 

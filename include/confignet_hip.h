@@ -286,7 +286,7 @@ int cn_sum_rows_into(const float* src, float* dst, int rows, int cols, int accum
 int cn_nc_reduce4(const void* x, float* out, int n, int s, int c, float slope, int flags, int dt, void* stream);
 int cn_nc_reduce(const void* x1, const void* x2, float* sum1, float* sum2, int n, int s, int c,
                  int flags, float slope, int dt, void* stream);
-/* a = x1 * act'(f2(x2)) (the activation derivative taken from the sign / value of x2 as in cn_act_bwd), written to dact_out,
+/* a = x1 * act'(x2) (the activation derivative taken from the sign / value of x2 ITSELF as in cn_act_bwd, not of f2(x2)), written to dact_out,
  * with sum1[n,c] = sum_s a and (if sum2 != NULL) sum2[n,c] = sum_s a*f2(x2) in the same pass: the tangent of LeakyReLU and its
  * two statistics (cn_dual_tail_*: ta, T1, T2) without a separate cn_act_bwd pass.  flags as cn_nc_reduce (bit1, bit4, period).
  * dact_out may be NULL (round 6): the two sums only, a is not stored. */
@@ -313,9 +313,13 @@ int cn_nc_lin2(const void* x1, const float* a1, const void* x2, const float* a2,
  * mode 1 InstanceNormalization (instance_normalization.py:117-130): p1 = gamma (C), p2 = beta (C);
  *        q = 1/(sqrt(var)+eps); A = gamma*q, B = beta - mu*A.
  * mode 2 get_layer_style (confignet_utils.py:147-159): A is (N,2C) = [mu | sqrt(var+eps)], B unused.
- * save_mean / save_r (N,C) keep mu and r|q|std for the backward pass. */
+ * save_mean / save_r (N,C) keep mu and r|q|std for the backward pass.
+ * x (mode 0; may be NULL), stored as dt: the normalised (n, S, c) tensor.  fp32 sums leave ~1e-6 mu^2 of absolute error in
+ * var; where mu^2 > 1000 (var + eps) -- an almost constant channel with a large mean -- that is no longer small under the root,
+ * and the thread of that (n, c) takes mean((x - mu)^2) from x instead.  cn_norm_apply (mode 0, dir 0) does the same. */
 int cn_norm_coef_fwd(int mode, const float* s1, const float* s2, const float* p1, const float* p2, float* A,
-                     float* B, float* save_mean, float* save_r, int n, int c, int S, float eps, void* stream);
+                     float* B, float* save_mean, float* save_r, int n, int c, int S, float eps, const void* x, int dt,
+                     void* stream);
 /* Backward coefficients: the input gradient is gx = c1*gy + c2*x + c0 (x = the normalised tensor, after
  * LeakyReLU for mode 1).  t1 = sum_s gy, t2 = sum_s gy*x.  mode 0: gp1 = d[s|b] (N,2C).  mode 1: gp1 = dgamma,
  * gp2 = dbeta (C), reduced over n.  mode 2: t1 = d[mu|std] (N,2C), t2 unused; c1 unused, gx = c2*x + c0. */
@@ -346,7 +350,8 @@ int cn_norm_apply(int mode, int dir, const void* x1, const void* x2, const float
  * LeakyReLU + instance norm (T1/T2/H1/H2p/E and C1/C2/C0/K1/K2/K0/kh/kt/ka/kc: n - n_style rows, indexed from 0); the primal
  * statistics mean/q/sm/ssd hold `period` samples and a row reads sample (row % period).  One head at a time: n_style = 0 or n,
  * period = n.  cn_dual_tail_gx: x / out / tx and et/ex/e0 hold n samples, h / ta and kh/kt/ka/kc hold nrep*n (head-major);
- * the heads' second-order terms are summed into out. */
+ * the heads' second-order terms are summed into out.  Any c (four channels per thread where c % 4 == 0, else one);
+ * cn_dual_tail_gx_tx needs c % 4 == 0. */
 int cn_dual_tail_coef_fwd(const float* T1, const float* T2, const float* U1, const float* U2, const float* mean,
                           const float* q, const float* sm, const float* ssd, const float* gamma, float* C1,
                           float* C2, float* C0, float* tstyle, int n, int c, int S, float eps, int n_style, int period,
