@@ -533,10 +533,11 @@ def _c3_partials():
     return _C3_PARTS[0]
 
 
-def conv_wgrad(x, gy, g, w_shape, out=None, accumulate=True, defer=True):
+def conv_wgrad(x, gy, g, w_shape, out=None, accumulate=True, defer=True, ws=None):
     """out: ADD the filter gradient to this tensor (a slot of a gradient arena, see grad_sink) instead of returning a new one;
     out with accumulate=False: WRITE it there (an uninitialised scratch the caller owns: the folded ResNet-50's packed gradients).
-    defer=False: complete in `out` when this returns, also inside a grad_sink (no slab reduction left to its join)."""
+    defer=False: complete in `out` when this returns, also inside a grad_sink (no slab reduction left to its join).
+    ws: the caller's own fp32 workspace for cn_conv_wgrad_ws (at least cn_conv_wgrad_workspace_bytes(g)) instead of a fresh one."""
     gw = out if out is not None else zero_pool_alloc(w_shape, x.device)
     pre = gw is not None and (accumulate or out is None)
     if gw is None:
@@ -566,7 +567,10 @@ def conv_wgrad(x, gy, g, w_shape, out=None, accumulate=True, defer=True):
     x, gy = f32(x), f32(gy)
     # caller-owned workspace for the partial filters of the kernel's row splits (0 bytes: a single split / the fall-back kernel)
     nbytes = int(lib.cn_conv_wgrad_workspace_bytes(ctypes.byref(g)))
-    ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32) if nbytes else None
+    if ws is None:
+        ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32) if nbytes else None
+    else:
+        assert ws.dtype == torch.float32 and ws.numel() * 4 >= nbytes, "conv_wgrad: workspace of %d bytes, %d needed" % (ws.numel() * 4, nbytes)
     if nbytes and out is not None and _SINK is not None and defer:
         # inside a backward pass (grad_sink): the row slices' slabs stay in `ws` and the pass adds the slabs of ALL its filter
         # gradients with one grouped launch at its join (grad_sink.join) instead of one reduction launch per layer on the chain

@@ -452,8 +452,8 @@ SWEEP_LAYERS = [
 @pytest.mark.parametrize("case", SWEEP_LAYERS, ids=[str(i) for i in range(len(SWEEP_LAYERS))])
 def test_conv_forced_tile_and_split_configurations_vs_oracle(case, monkeypatch):
     """cn_conv_tune sweep: tiles 128x128 / 128x64 / 64x64 / 128x32 / 128x96, split-K 1 / 3 / 8, forward and parity-ordered
-    data gradient, filter-gradient workgroup targets -- each against the float64 oracle (Winograd off: the direct kernels are
-    what is being configured)."""
+    data gradient, every filter-gradient tile (256x64 included) and the filter-gradient workgroup targets -- each against the
+    float64 oracle (Winograd off: the direct kernels are what is being configured)."""
     from confignet_amd import ops
     from confignet_amd._lib import lib
     monkeypatch.setattr(ops, "WINOGRAD", False)
@@ -467,8 +467,12 @@ def test_conv_forced_tile_and_split_configurations_vs_oracle(case, monkeypatch):
     gy = rnd(*y0.shape)
     yr, gur, gwr = _full_size_oracle(xs, k, cout, stride, 0, x, w, gy)
     try:
-        for cfg in (0, 1, 2, 3, 4):
-            if cfg == 4 and cout % 96:
+        for cfg in (0, 1, 2, 3, 4, 5):
+            # the filter gradient reads the same hook: 0 / 4 / 2 / 3 / 5 -> its 128x128 / 128x96 / 64x64 / 128x32 / 256x64 tile (1: its
+            # own choice), any of them on any cout.  5 exists for it alone: the forward plan has no such tile.
+            ops.check(lib.cn_conv_tune(cfg, 0, 0), "cn_conv_tune")
+            close(ops.conv_wgrad(x, gy, g, tuple(w.shape)), gwr, tol=5e-4, what="wgrad cfg %d" % cfg)
+            if cfg == 5 or (cfg == 4 and cout % 96):
                 continue
             for splits in (1, 3, 8):
                 ops.check(lib.cn_conv_tune(cfg, splits, 0), "cn_conv_tune")
