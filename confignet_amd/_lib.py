@@ -144,6 +144,9 @@ SIGNATURES = {
     "cn_ema_step": [_p, _p, _z, _f, _p],
     "cn_gather_images_u8": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
     "cn_to_uint8": [_p, _p, _z, _p],
+    "cn_hdri_rows_v": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
+    "cn_hdri_rows_h": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
+    "cn_exp2m1": [_p, _p, _z, _p],
     "cn_spin": [ctypes.c_ulonglong, _p],
     "cn_conv_weight_prep_bf16": [_p, _p, _p, _i, _i, _i, _p],
     "cn_conv_fwd_bf16": [_G, _p, _p, _p, _p, _i, _f, _p],

@@ -1516,6 +1516,45 @@ def gather_images_u8(pool, idx, flip):
     return out
 
 
+def _i32ptr(t):
+    assert t.dtype == torch.int32, "int32 tensor expected, got %s" % (t.dtype,)
+    return _ptr(t)
+
+
+def hdri_rows_v(pool, y0, wy, oh):
+    """cn_hdri_rows_v: pool (P, H, W, 3) fp32 radiance -> (P, oh, W, 3): log2(x + 1), then the vertical half of the area resize
+    (y0 (oh) int32 first source rows, wy (oh, T) fp32 weights: hdri.area_table)."""
+    pool = _c(pool)
+    p, h, w, c = pool.shape
+    assert c == 3 and tuple(y0.shape) == (oh,) and wy.shape[0] == oh and wy.dim() == 2
+    v = torch.empty((p, oh, w, 3), device=pool.device, dtype=torch.float32)
+    check(lib.cn_hdri_rows_v(_fptr(pool), _ptr(v), _i32ptr(y0), _fptr(wy), p, h, w, oh, wy.shape[1], _stream()), "cn_hdri_rows_v")
+    return v
+
+
+def hdri_rows_h(v, idx, shift, x0, wx, ow, mean=None):
+    """cn_hdri_rows_h: v (P, oh, W, 3) from hdri_rows_v -> (n, oh, ow, 3): sample i is image idx[i] rolled by shift[i] columns
+    (np.roll along the width, any integer) and area-resized to ow columns, minus mean (oh, ow, 3) when given.  idx, shift: (n)
+    int32; x0 (ow) int32, wx (ow, T) fp32: hdri.area_table."""
+    v = _c(v)
+    p, oh, w, c = v.shape
+    n = idx.numel()
+    assert c == 3 and shift.numel() == n and tuple(x0.shape) == (ow,) and wx.shape[0] == ow and wx.dim() == 2
+    assert mean is None or mean.numel() == oh * ow * 3
+    out = torch.empty((n, oh, ow, 3), device=v.device, dtype=torch.float32)
+    check(lib.cn_hdri_rows_h(_fptr(v), _ptr(out), _i32ptr(idx), _i32ptr(shift), _i32ptr(x0), _fptr(wx),
+                             _fptr(None if mean is None else _c(mean)), n, p, w, oh, ow, wx.shape[1], _stream()), "cn_hdri_rows_h")
+    return out
+
+
+def exp2m1(x):
+    """2^x - 1 elementwise (cn_exp2m1)."""
+    x = _c(x)
+    y = torch.empty_like(x)
+    check(lib.cn_exp2m1(_fptr(x), _ptr(y), x.numel(), _stream()), "cn_exp2m1")
+    return y
+
+
 def to_uint8(x):
     x = f32(x)
     out = torch.empty(x.shape, device=x.device, dtype=torch.uint8)

@@ -472,6 +472,22 @@ int cn_scale_columns_segments(const float* src, float* dst, const int* seg, cons
 int cn_bn_fold_bwd(const int* seg, int nseg, int blocks, const float* gwf, const float* gshift, const float* arena,
                    const float* a, const float* rs, const float* bm, float* gout, void* stream);
 
+/* ---- HDRI environment-map encoding (hdri_encoding/hdri_pca_model.py: np.log2(x + 1), rotate_hdri = np.roll along the columns,
+ * cv2.resize INTER_AREA; confignet_amd/hdri.py) -------------------------------------------------------------------------------
+ * The area resize as two separable passes around the roll.  A table holds, per output index, the first source index (y0 / x0,
+ * int32) and t_len weights (wy / wx, fp32, overlap / scale, zero padded), t_len >= ceil(in / out) + 1; all pointers are device
+ * memory.  Enlarging (oh > h, ow > w), NULL pointers and a t_len too small for the scale return CN_EINVAL and launch nothing.
+ * rows_v, once per pool image: v (pool, oh, w, 3) = sum_t wy[o][t] log2f(x[p][y0[o] + t] + 1) from x (pool, h, w, 3). */
+int cn_hdri_rows_v(const float* x, float* v, const int* y0, const float* wy, int pool, int h, int w, int oh, int t_len,
+                   void* stream);
+/* rows_h, once per sample: out (n, oh, ow, 3) = sum_t wx[q][t] v[idx[i]][o][(x0[q] + t - shift[i]) mod w] - mean[o][q][c]
+ * (mean (oh, ow, 3) may be NULL); idx, shift: (n) int32, shift any integer (np.roll semantics: negative, |shift| > w).  A sample
+ * whose idx is outside [0, pool) reads nothing and comes out as NaN. */
+int cn_hdri_rows_h(const float* v, float* out, const int* idx, const int* shift, const int* x0, const float* wx,
+                   const float* mean, int n, int pool, int w, int oh, int ow, int t_len, void* stream);
+/* y = exp2f(x) - 1 (HDRIModelPCA.inverse_transform: np.power(2, x) - 1) */
+int cn_exp2m1(const float* x, float* y, size_t numel, void* stream);
+
 /* ---- profiling of the dominant kernel class (implicit-GEMM convolutions) with HIP events
  * recorded on the launch stream (bench.py roofline object) -----------------------------------*/
 int cn_prof_enable(int on);
