@@ -79,6 +79,9 @@ SIGNATURES = {
     "cn_conv_wgrad_workspace_bytes": [_G],
     "cn_conv_wgrad_ws": [_G, _p, _p, _p, _i, _p, _z, _p],
     "cn_conv_wgrad_ws_slabs": [_G, _p, _p, _p, _i, _p, _z, ctypes.POINTER(_i), _p],
+    "cn_conv_wgrad_dt_workspace_bytes": [_G, _i, _i, ctypes.POINTER(_z)],
+    "cn_conv_wgrad_dt": [_G, _p, _i, _p, _i, _p, _i, _p, _z, ctypes.POINTER(_i), _p],
+    "cn_conv_wgrad_plan": [_G, _i, _i, _i, ctypes.c_uint, _i, ctypes.POINTER(ctypes.c_longlong)],
     "cn_sum_parts_grouped": [_p, _i, _p],
     "cn_gemm_depth_grouped": [_p, _i, _p],
     "cn_gan_loss_grouped": [_p, _i, _i, _p],

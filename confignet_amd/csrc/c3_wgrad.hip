@@ -18,7 +18,7 @@
 
 namespace {
 
-constexpr int C3W_TILE = 64;           // output pixels per tile
+constexpr int C3W_TILE = CN_C3_WGRAD_TILE;           // output pixels per tile
 
 template <int S, typename T>
 __global__ __launch_bounds__(256) void c3_wgrad_kernel(CnConvGeom g, const float* __restrict__ X, const T* __restrict__ GY,
@@ -163,29 +163,10 @@ __global__ __launch_bounds__(256) void c3_wgrad_reduce_kernel(const float* __res
 
 }  // namespace
 
-// Number of partial filters (27 x cout floats each) the caller provides as scratch.
-extern "C" int cn_conv_wgrad_c3_partials(void) { return 512; }
-
-// Filter gradient of a 3x3 convolution of a 3-channel fp32 image (g->cin == 3, stride 1 or 2, no dilation / upsample,
-// cout <= 64 and a multiple of 4); gy in fp32 or bf16 (gy_dt).  scratch: cn_conv_wgrad_c3_partials() * 27 * cout floats.  accumulate: add to gw.
-// Returns CN_EUNSUPPORTED (nothing launched) for other geometries.
-extern "C" int cn_conv_wgrad_c3(const CnConvGeom* gp, const float* x, const void* gy, int gy_dt, float* scratch, float* gw,
-                                int accumulate, void* stream) {
-    CN_CHECK_ARG(gp && x && gy && scratch && gw && (gy_dt == CN_F32 || gy_dt == CN_BF16), "conv_wgrad_c3: bad args");
-    const CnConvGeom& g = *gp;
-    if (!(g.nd == 2 && g.cin == 3 && g.k_h == 3 && g.k_w == 3 && g.k_d == 1 && g.s_h == g.s_w && (g.s_h == 1 || g.s_h == 2) &&
-          g.dl_h == 1 && g.dl_w == 1 && g.up == 0 && g.cout <= 64 && g.cout >= 4 && g.cout % 4 == 0))
-        return CN_EUNSUPPORTED;
-    CN_CHECK_ARG((double)g.n * g.out_h * g.out_w * g.cout < 2147483647.0, "tensor exceeds 2^31 elements");
-    const int tiles_x = cn_cdiv(g.out_w, C3W_TILE), ntiles = g.n * g.out_h * tiles_x;
-    const int nparts = cn_conv_wgrad_c3_partials();
-    const int pw = C3W_TILE * g.s_h + 2, gpitch = (g.cout + 3) & ~3;
-    size_t lds = sizeof(float) * 4 * (size_t)(3 * pw * 3 + C3W_TILE * gpitch);
-    if (lds < sizeof(float) * 4 * 2 * 16 * 64) lds = sizeof(float) * 4 * 2 * 16 * 64;
-    hipStream_t s = (hipStream_t)stream;
-    cn_prof_begin(s, 2.0 * 27.0 * g.cout * (double)g.n * g.out_h * g.out_w,
-                  4.0 * (double)g.n * g.in_h * g.in_w * 3 + (gy_dt == CN_BF16 ? 2.0 : 4.0) * g.n * g.out_h * g.out_w * g.cout + 4.0 * 27 * g.cout,
-                  CN_FAM_C3_WGRAD);
+// One launch on nparts workgroups (each writes one partial filter of 27 x cout floats to scratch) + the launch that adds them; the
+// numbers are the plan's (conv_dispatch.hip: plan_conv_wgrad).
+int cn_c3_wgrad(const CnConvGeom& g, const float* x, const void* gy, int gy_dt, float* scratch, int tiles_x, int ntiles, int nparts,
+                size_t lds, hipStream_t s) {
 #define C3W(S_, T_)                                                                                                              \
     do {                                                                                                                         \
         static bool attr_set = false;                                                                                            \
@@ -203,10 +184,9 @@ extern "C" int cn_conv_wgrad_c3(const CnConvGeom* gp, const float* x, const void
         if (g.s_h == 1) C3W(1, bf16_t); else C3W(2, bf16_t);
     }
 #undef C3W
-    cn_prof_end(s);
-    CN_LAUNCH_CHECK();
-    const int count = 27 * g.cout;
-    hipLaunchKernelGGL(c3_wgrad_reduce_kernel, dim3(cn_cdiv(count, 16)), dim3(256), 0, s, scratch, gw, nparts, count, accumulate);
-    CN_LAUNCH_CHECK();
     return CN_OK;
+}
+
+void cn_c3_wgrad_reduce(const float* scratch, float* gw, int nparts, int count, int accumulate, hipStream_t s) {
+    hipLaunchKernelGGL(c3_wgrad_reduce_kernel, dim3(cn_cdiv(count, 16)), dim3(256), 0, s, scratch, gw, nparts, count, accumulate);
 }

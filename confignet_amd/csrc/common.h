@@ -56,15 +56,11 @@ int cn_fwd2(const CnConvGeom* gp, int cfg, int bt, const float* A, const float* 
 void cn_fwd2_tune(int kb, int ns, int np);
 void cn_fwd2_grid(int cfg, long M, int N, int par, int splits, int grid[3]);      // the launch grid cn_fwd2 uses
 // igemm_conv.hip: the register-staged implicit-GEMM loop on tile cfg (anything but 0 / 1 / 3 / 4: 64 x 64), the same split-K protocol;
-// cn_igemm_fwd_thin: its 128 x 32 tile with guarded filter loads for parity-ordered data gradients into a thin (cout <= 4) image;
-// cn_igemm_wgrad: the filter gradient split over rows (wg_target: workgroups aimed at, 0 = default); cn_tiny_wgrad: the from-RGB
-// shapes (1x1, <= 4 channels on both sides), CN_EUNSUPPORTED without launching for every other geometry
+// cn_igemm_fwd_thin: its 128 x 32 tile with guarded filter loads for parity-ordered data gradients into a thin (cout <= 4) image
 int cn_igemm_fwd(int cfg, const CnConvGeom& g, bool vec, int par, int splits, const float* x, const float* w, const float* bias, float* y,
                  int act, float slope, hipStream_t s, int bt, long part_stride, const float* res);
 void cn_igemm_fwd_grid(int cfg, const CnConvGeom& g, bool vec, int par, int splits, int grid[3]);
 int cn_igemm_fwd_thin(const CnConvGeom& g, const float* x, const float* w, const float* bias, float* y, int act, float slope, hipStream_t s);
-int cn_igemm_wgrad(int cfg, const CnConvGeom& g, const float* x, const float* gy, float* gw, long wg_target, hipStream_t s);
-int cn_tiny_wgrad(const CnConvGeom& g, const float* x, const float* gy, float* gw, hipStream_t s);
 // Which launch a forward / data-gradient convolution gets (conv_dispatch.hip: plan_conv_fwd; the numbers are what cn_conv_fwd_plan
 // reports).  small_conv.hip launches everything before CN_ROUTE_FWD2 except CN_ROUTE_THIN_PAR_IGEMM.
 enum ConvRoute { CN_ROUTE_UP2K4_RGB = 0, CN_ROUTE_S2_IMAGE_DGRAD, CN_ROUTE_S1_IMAGE_DGRAD, CN_ROUTE_THIN_PAR_IGEMM, CN_ROUTE_THIN_COOP,
@@ -74,6 +70,32 @@ void cn_small_conv(int route, unsigned grid_x, const CnConvGeom& g, bool vec, in
                    const float* bias, void* y, int y_dt, int act, float slope, hipStream_t s);
 int cn_fwd2_bf16(const CnConvGeom& g, int cfg, int flip, const void* x, const void* wb, const float* bias, void* y, int act, float slope,
                  int par, hipStream_t s);
+
+// Which launch a filter gradient gets (conv_dispatch.hip: plan_conv_wgrad; the numbers are what cn_conv_wgrad_plan reports): the
+// K = 27 first layers (c3_wgrad.hip), thin outputs (thin_wgrad.hip), the from-RGB 1x1 shapes and the atomic row-split kernel
+// (igemm_conv.hip), the LDS-DMA kernel (wgrad2.hip), the bf16 kernel (igemm_bf16.hip).  The functions below launch ONE instantiation
+// with the plan's numbers and decide nothing.
+enum WgradRoute { CN_WG_C3 = 0, CN_WG_THIN, CN_WG_TINY, CN_WG_WGRAD2, CN_WG_IGEMM, CN_WG_BF16, CN_WG_NONE };
+constexpr int CN_C3_WGRAD_TILE = 64, CN_C3_WGRAD_PARTS = 512;                          // output pixels of a tile; workgroups = partial filters
+constexpr int CN_THIN_WGRAD_TH = 8, CN_THIN_WGRAD_TW = 32, CN_THIN_WGRAD_PARTS = 512;  // output pixels of a tile; most workgroups = partial filters
+struct Wg2Plan {
+    int cfg;          // implicit-GEMM numbering: 0 = 128x128, 4 = 128x96, 2 = 64x64, 3 = 128x32, 5 = 256x64
+    long tiles_x, tiles_y, splits, rows;
+};
+bool cn_wgrad2_ok(const CnConvGeom& g);
+Wg2Plan cn_wgrad2_plan(const CnConvGeom& g, int forced_cfg, long wg_target);
+void cn_wgrad2(int cfg, int ns, const CnConvGeom& g, const float* x, const float* gy, float* out, long slab_stride, int rows, int tiles_x,
+               int tiles_y, int splits, int accumulate, unsigned grid, hipStream_t s);
+void cn_igemm_wgrad(int cfg, const CnConvGeom& g, const float* x, const float* gy, float* gw, int rows, float* parts, int tx, int ty,
+                    int splits, dim3 grid, hipStream_t s);
+int cn_tiny_wgrad(const CnConvGeom& g, const float* x, const float* gy, float* gw, int blocks, float* parts, hipStream_t s);
+void cn_bf16_wgrad(int cfg, const CnConvGeom& g, const void* x, const void* gy, float* gw, int rows, int tx, int ty, int splits, dim3 grid,
+                   hipStream_t s);
+int cn_c3_wgrad(const CnConvGeom& g, const float* x, const void* gy, int gy_dt, float* scratch, int tiles_x, int ntiles, int nparts,
+                size_t lds, hipStream_t s);
+void cn_c3_wgrad_reduce(const float* scratch, float* gw, int nparts, int count, int accumulate, hipStream_t s);
+void cn_thin_wgrad(const CnConvGeom& g, const float* x, const float* gy, float* scratch, int nwg, size_t lds, int tiles_y, int tiles_x,
+                   int ntiles, hipStream_t s);
 
 // profiling hooks (prof.hip): bracket one launch of the dominant kernel class
 // family: which kernel of the class is launched (cn_prof_collect_by_family); bytes: the launch's algorithmic HBM bytes

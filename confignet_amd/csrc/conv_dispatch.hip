@@ -4,25 +4,21 @@
 // the request alone (route, tile, K split, profile family, grid -- no HIP call, no pointer), run_conv_fwd performs it (one switch
 // over the route, one profile bracket, one launch check, the split-K protocol).  cn_conv_fwd_plan reports the plan without a
 // device.  The kernels live in small_conv.hip (thin and image-side layers), fwd2.hip (the LDS-DMA loop) and igemm_conv.hip (the
-// register-staged implicit-GEMM loop); the filter-gradient entries and the tuning hooks are at the end of this file.
+// register-staged implicit-GEMM loop).  The filter gradient is served the same way by plan_conv_wgrad / run_conv_wgrad /
+// cn_conv_wgrad_plan in the second half of this file; the tuning hooks are at its end.
 #include "common.h"
+
+#include <algorithm>
 
 #include "mma_tile.h"
 #include "conv_geom.h"
-
-// wgrad2.hip
-bool cn_wgrad2_ok(const CnConvGeom& g);
-size_t cn_wgrad2_workspace_floats(const CnConvGeom& g);
-int cn_wgrad2_family(const CnConvGeom& g);
-void cn_wgrad2_tune(int cfg, long wg_target);
-void cn_wgrad2_stages(int ns);
-int cn_wgrad2(const CnConvGeom& g, const float* x, const float* gy, float* gw, int accumulate, float* ws, hipStream_t s, int* parts_out = nullptr);
 
 namespace {
 
 int g_tune_cfg = -1;                 // cn_conv_tune (sweeps, tests): forced tile / split-K factor / filter-gradient workgroup target
 int g_tune_splits = 0;
 long g_tune_wg_blocks = 0;
+int g_tune_wg2_ns = 0;               // cn_conv_loop_select(ns): stage count of the LDS-DMA filter-gradient kernel (0 = default)
 int g_fwd2_sel = -1;                 // cn_conv_loop_select override: 0 = keep the LDS-DMA loop (fwd2.hip) off
 constexpr int g_fwd2_min_nks = 1;    // the LDS-DMA loop takes reductions of MORE K steps than this
 constexpr int g_fwd2_min_c = 48;     // thinnest layer it takes
@@ -401,67 +397,374 @@ extern "C" int cn_conv_fwd_plan(const CnConvGeom* gp, int bt, int has_bias, int 
     return p.ret;
 }
 
-extern "C" int cn_conv_wgrad(const CnConvGeom* gp, const float* x, const float* gy, float* gw, int accumulate, void* stream) {
-    if (int e = check_geom(gp)) return e;
-    CN_CHECK_ARG(x && gy && gw, "NULL tensor");
-    const CnConvGeom g = *gp;
-    hipStream_t s = (hipStream_t)stream;
-    if (!accumulate) {
-        const long Ktot = (long)g.k_d * g.k_h * g.k_w * g.cin;
-        if (int ez__ = cn_zero_async(gw, sizeof(float) * Ktot * g.cout, s)) return ez__;
+// ---- the filter gradient --------------------------------------------------------------------------------------------------------
+// plan_conv_wgrad decides the launch from the geometry and the request alone (route, tile, row slices, grid, profile family, the
+// workspace the caller provides, zero pass, the reduction that follows -- no HIP call, no pointer); run_conv_wgrad performs it and is
+// the only place a filter-gradient kernel is launched from.  The entry points build a request -- the storage types, whether the
+// slabs stay with the caller, and the routes the entry has always taken -- plan and run; cn_conv_wgrad_dt takes every route.
+namespace {
+
+struct WgradReq {
+    int x_dt, gy_dt;
+    bool caller_slabs;       // a row-split LDS-DMA launch leaves its slabs in the workspace for the caller to add
+    unsigned routes;         // bit r set: route r (WgradRoute) may be taken
+    bool det = cn_det() != 0;        // deterministic mode (cn_conv_wgrad_plan may ask for either)
+};
+constexpr unsigned wg_bit(int r) { return 1u << r; }
+constexpr unsigned WG_ATOMIC = wg_bit(CN_WG_TINY) | wg_bit(CN_WG_IGEMM), WG_FP32_GEMM = wg_bit(CN_WG_WGRAD2) | WG_ATOMIC, WG_ALL = ~0u;
+
+enum { WG_SUM_NONE = 0, WG_SUM_PARTS, WG_SUM_C3, WG_SUM_CALLER };      // what follows the launch: nothing, cn_sum_parts, c3_wgrad_reduce_kernel, the caller's own sum
+
+struct WgradPlan {
+    int route = CN_WG_NONE;
+    int ret = CN_EUNSUPPORTED;       // what the request gets when nothing is launched (route == CN_WG_NONE)
+    int cfg = -1;                    // tile of the GEMM routes, implicit-GEMM numbering (5 = 256 x 64)
+    int stages = 0;                  // WGRAD2: stages of the LDS-DMA loop
+    long splits = 1, rows = 0;       // GEMM routes: row slices and rows per slice
+    int tx = 0, ty = 0;              // WGRAD2: tiles over filter rows / output channels; IGEMM / BF16: the same when the grid is the XCD-ordered 1-D one, else 0; C3 / THIN: tiles of output pixels per row / column
+    int family = -1;                 // CN_FAM_* of the profile bracket; -1: the launch has none
+    int grid[3] = {0, 0, 0};
+    size_t lds = 0;                  // C3 / THIN: dynamic LDS bytes
+    size_t ws_floats = 0;            // workspace the caller provides: slabs (WGRAD2), partial filters (C3, THIN)
+    size_t det_floats = 0;           // TINY / IGEMM in deterministic mode: partials in the stream's workspace instead of atomics
+    bool zero = false;               // the atomic routes: a zero pass precedes the launch when the target is to be written
+    int sum = WG_SUM_NONE;
+};
+
+struct WgTile { int bm, bn; };       // rows of (tap, ci) x output channels
+WgTile wgrad_tile(int cfg) { return cfg == 3 ? WgTile{128, 32} : cfg == 4 ? WgTile{128, 96} : cfg == 0 ? WgTile{128, 128} : cfg == 5 ? WgTile{256, 64} : WgTile{64, 64}; }
+int wgrad_family(int cfg) {
+    return cfg == 3 ? CN_FAM_WGRAD_128x32 : cfg == 4 ? CN_FAM_WGRAD_128x96 : cfg == 0 ? CN_FAM_WGRAD_128x128 : cfg == 5 ? CN_FAM_WGRAD_256x64 : CN_FAM_WGRAD_64x64;
+}
+
+// Grid of the atomic and the bf16 kernel: (filter-row tiles, channel tiles, slices), or from 16 slices of more than one tile up the
+// XCD-aware 1-D order (igemm_wgrad_kernel: every tile of ONE row slice on the same XCD), padded to whole groups of 8 slices
+void sliced_grid(const CnConvGeom& g, WgTile t, WgradPlan& p) {
+    const long Ktot = (long)g.k_d * g.k_h * g.k_w * g.cin;
+    const int gx = cn_cdiv(Ktot, t.bm), gy = cn_cdiv(g.cout, t.bn);
+    p.grid[0] = gx; p.grid[1] = gy; p.grid[2] = (int)p.splits;
+    if ((long)gx * gy > 1 && p.splits >= 16) {
+        p.tx = gx; p.ty = gy;
+        p.grid[0] = cn_cdiv(p.splits, 8) * 8 * gx * gy; p.grid[1] = p.grid[2] = 1;
     }
-    int e = cn_tiny_wgrad(g, x, gy, gw, s);
-    if (e != CN_EUNSUPPORTED) return e;
+}
+
+// Row slices of the atomic kernel (igemm_wgrad_kernel): from a workgroup target, at least 256 rows each.  false (+ error string): in
+// deterministic mode not even one partial filter fits the stream's workspace.
+bool igemm_wgrad_slices(const CnConvGeom& g, WgTile t, long wg_target, bool det, WgradPlan& p) {
+    const long M = (long)g.n * g.out_d * g.out_h * g.out_w;
+    const long Ktot = (long)g.k_d * g.k_h * g.k_w * g.cin;
+    const long tiles = (long)cn_cdiv(Ktot, t.bm) * cn_cdiv(g.cout, t.bn);
+    const long wg_blocks = wg_target > 0 ? wg_target : 2048;   // sweep 256..4096: flat from 1536 up
+    long splits = (wg_blocks + tiles - 1) / tiles;
+    if (det) {
+        // deterministic mode: per-split partial filters in the stream's workspace, added in split order by a second launch
+        // (every split of every tile writes its whole slab region: no clearing).  As many splits as the workspace holds.
+        const long cap = (long)(CN_DET_WS_FLOATS / ((size_t)Ktot * g.cout));
+        if (cap < 1) {
+            cn_set_error("deterministic filter gradient: %ld x %d filter does not fit the workspace", Ktot, g.cout);
+            return false;
+        }
+        if (splits > cap) splits = cap;
+    }
+    long rows = (M + splits - 1) / splits;
+    if (rows < 256) rows = 256;
+    rows = (rows + BK - 1) / BK * BK;
+    p.rows = rows;
+    p.splits = (M + rows - 1) / rows;
+    return true;
+}
+
+// Row slices of the bf16 kernel (round-5 sweep, profiles/round5_bf16_wgrad_splits.txt).  What the sweep showed: (1) a slice shorter
+// than ~512 rows is mostly prologue + the tile's atomic adds; (2) one workgroup more than the CUs hold at once costs a whole extra
+// round -- the kernels hold 3 (128 x 128), 4 (128 x 96) or 5 workgroups per CU -- and the narrow tiles like two rounds; (3) with the
+// XCD order a slice count that is not a multiple of 8 leaves XCDs with one slice more than others.
+void bf16_wgrad_slices(const CnConvGeom& g, WgTile t, WgradPlan& p) {
+    constexpr long KS = 32, min_rows = 512;          // (KS: bf16 reduction rows per LDS stage, igemm_bf16.hip)
+    const long M = (long)g.n * g.out_d * g.out_h * g.out_w;
+    const long Ktot = (long)g.k_d * g.k_h * g.k_w * g.cin;
+    const long tiles = (long)cn_cdiv(Ktot, t.bm) * cn_cdiv(g.cout, t.bn);
+    const long per_cu = t.bm * t.bn >= 128 * 128 ? 3 : t.bm * t.bn >= 128 * 96 ? 4 : 5;
+    const long target = 256 * per_cu * (t.bn >= 96 ? 1 : 2);
+    long splits = target / tiles;
+    if (splits > M / min_rows) splits = M / min_rows;
+    const long fill = std::min<long>(M / 256, (256 + tiles - 1) / tiles);        // ... but at least one workgroup per CU
+    if (splits < fill) splits = fill;
+    if (splits >= 16) splits &= ~7L;
+    if (splits < 1) splits = 1;
+    long rows = (M + splits - 1) / splits;
+    if (rows < 256) rows = std::min<long>(256, (M + KS - 1) / KS * KS);
+    rows = (rows + KS - 1) / KS * KS;
+    p.rows = rows;
+    p.splits = (M + rows - 1) / rows;
+}
+
+// Pure: reads the geometry, the request (deterministic mode is part of it), cn_cu_count() and the tuning overrides.  The routes are asked in the order the
+// callers always asked them: K = 27, thin, bf16, then the fp32 GEMM kernels.
+WgradPlan plan_conv_wgrad(const CnConvGeom& g, const WgradReq& q) {
+    WgradPlan p;
+    const long M = (long)g.n * g.out_d * g.out_h * g.out_w;
+    const long Ktot = (long)g.k_d * g.k_h * g.k_w * g.cin;
+    const size_t count = (size_t)Ktot * g.cout;
+    const bool x32 = q.x_dt == CN_F32, y32 = q.gy_dt == CN_F32, x16 = q.x_dt == CN_BF16, y16 = q.gy_dt == CN_BF16;
+    auto may = [&q](int route) { return (q.routes & wg_bit(route)) != 0; };
+    auto take = [&p](int route, int family) {
+        p.route = route;
+        p.ret = CN_OK;
+        p.family = family;
+    };
+    // K = 27 first layers (3x3 on the 3-channel fp32 image, stride 1 / 2; gy in either storage type): staged-tile kernel without
+    // atomics -- the generic split-over-rows kernel runs them at 10 TFLOP/s
+    if (may(CN_WG_C3) && x32 && (y32 || y16) && g.nd == 2 && g.cin == 3 && g.k_h == 3 && g.k_w == 3 && g.k_d == 1 && g.s_h == g.s_w &&
+        (g.s_h == 1 || g.s_h == 2) && g.dl_h == 1 && g.dl_w == 1 && g.up == 0 && g.cout <= 64 && g.cout >= 4 && g.cout % 4 == 0) {
+        take(CN_WG_C3, CN_FAM_C3_WGRAD);
+        p.tx = cn_cdiv(g.out_w, CN_C3_WGRAD_TILE);
+        p.grid[0] = CN_C3_WGRAD_PARTS; p.grid[1] = p.grid[2] = 1;
+        const int pw = CN_C3_WGRAD_TILE * g.s_h + 2, gpitch = (g.cout + 3) & ~3;
+        p.lds = sizeof(float) * 4 * (size_t)(3 * pw * 3 + CN_C3_WGRAD_TILE * gpitch);
+        if (p.lds < sizeof(float) * 4 * 2 * 16 * 64) p.lds = sizeof(float) * 4 * 2 * 16 * 64;
+        p.ws_floats = CN_C3_WGRAD_PARTS * count;
+        p.sum = WG_SUM_C3;
+        return p;
+    }
+    // thin output (map_final): staged-tile VALU kernel with ordered partial sums -- the implicit-GEMM kernel runs it at 6 TFLOP/s.
+    // A patch that does not fit the LDS goes on to the next route.
+    const int T = g.k_h * g.k_w;
+    if (may(CN_WG_THIN) && x32 && y32 && g.nd == 2 && g.cout <= 4 && g.cin % 4 == 0 && g.cin >= 8 && g.cin <= 64 && g.s_h == 1 && g.s_w == 1 &&
+        g.dl_h == 1 && g.dl_w == 1 && T <= 16 && T * (g.cin / 4) <= 256) {
+        const int PH0 = ((CN_THIN_WGRAD_TH + g.k_h - 1) >> g.up) + 2, PW0 = ((CN_THIN_WGRAD_TW + g.k_w - 1) >> g.up) + 2;
+        size_t lds = sizeof(float) * ((size_t)PH0 * PW0 * g.cin + CN_THIN_WGRAD_TH * CN_THIN_WGRAD_TW * 4);
+        const size_t red = sizeof(float) * 256 * 4 * g.cout;
+        if (lds < red) lds = red;
+        if (lds <= 64 * 1024) {
+            take(CN_WG_THIN, -1);
+            p.ty = cn_cdiv(g.out_h, CN_THIN_WGRAD_TH); p.tx = cn_cdiv(g.out_w, CN_THIN_WGRAD_TW);
+            const int ntiles = g.n * p.ty * p.tx;
+            p.grid[0] = ntiles < CN_THIN_WGRAD_PARTS ? ntiles : CN_THIN_WGRAD_PARTS; p.grid[1] = p.grid[2] = 1;
+            p.lds = lds;
+            p.ws_floats = CN_THIN_WGRAD_PARTS * count;
+            p.sum = WG_SUM_PARTS;
+            return p;
+        }
+    }
+    if (x16 && y16) {        // bf16 operands: 16-byte pieces of 8 channels, fp32 atomics on the tile in every mode
+        if (!may(CN_WG_BF16) || g.cin % 8 || g.cout % 8) return p;
+        take(CN_WG_BF16, CN_FAM_BF16_WGRAD);
+        p.cfg = wgrad_tile_cfg(g);
+        bf16_wgrad_slices(g, wgrad_tile(p.cfg), p);
+        sliced_grid(g, wgrad_tile(p.cfg), p);
+        p.zero = true;
+        return p;
+    }
+    if (!x32 || !y32) return p;
+    // Every geometry the LDS-DMA kernel can take (round 6: with the slot layout and the XCD-aware slice plan it is at or ahead of
+    // the round-3 kernel -- split over rows, fp32 atomics -- on every shape of the iteration, profiles/round6_wgrad_shapes.txt): row
+    // slices through slabs in the caller's workspace + one ordered reduction, bit-reproducible in every mode.
+    // The round-3 kernel keeps the rest: channel counts that are no multiple of 4, K < 64, > 2 GiB operands.
+    if (may(CN_WG_WGRAD2) && cn_wgrad2_ok(g) && Ktot >= 64) {
+        const int t = g_tune_cfg;          // (cn_conv_tune: the tiles this kernel has, anything else = its own choice)
+        const Wg2Plan w = cn_wgrad2_plan(g, t == 0 || t == 2 || t == 3 || t == 4 || t == 5 ? t : -1, g_tune_wg_blocks);
+        take(CN_WG_WGRAD2, wgrad_family(w.cfg));
+        p.cfg = w.cfg;
+        p.stages = w.cfg == 3 || g_tune_wg2_ns == 3 ? 3 : 4;
+        p.splits = w.splits; p.rows = w.rows;
+        p.tx = (int)w.tiles_x; p.ty = (int)w.tiles_y;
+        // (from 8 slices up the XCD-aware order, padded to whole groups of 8 slices)
+        p.grid[0] = (int)((w.splits >= 8 ? cn_cdiv(w.splits, 8) * 8 : w.splits) * w.tiles_x * w.tiles_y); p.grid[1] = p.grid[2] = 1;
+        if (w.splits > 1) {
+            p.ws_floats = (size_t)w.splits * count;
+            p.sum = q.caller_slabs ? WG_SUM_CALLER : WG_SUM_PARTS;
+        }
+        return p;
+    }
+    // the from-RGB shapes (1x1, cin and cout <= 4)
+    if (may(CN_WG_TINY) && Ktot <= 4 && g.cout <= 4 && g.k_d * g.k_h * g.k_w == 1 && g.s_h == 1 && g.s_w == 1 && g.s_d == 1 && !g.up &&
+        g.p_h == 0 && g.p_w == 0 && g.p_d == 0) {
+        take(CN_WG_TINY, -1);
+        p.grid[0] = cn_cdiv(M, 256) > 1024 ? 1024 : cn_cdiv(M, 256); p.grid[1] = p.grid[2] = 1;
+        p.zero = true;
+        if (q.det) {                     // deterministic mode: per-workgroup partials, added in workgroup order
+            p.det_floats = (size_t)p.grid[0] * 16;
+            p.sum = WG_SUM_PARTS;
+        }
+        return p;
+    }
+    if (!may(CN_WG_IGEMM)) return p;
     const int cfg = wgrad_tile_cfg(g);
-    cn_prof_begin(s, conv_flops(g), conv_bytes(g), cfg == 3 ? CN_FAM_WGRAD_128x32 : cfg == 4 ? CN_FAM_WGRAD_128x96 : cfg == 0 ? CN_FAM_WGRAD_128x128 : CN_FAM_WGRAD_64x64);
-    e = cn_igemm_wgrad(cfg, g, x, gy, gw, g_tune_wg_blocks, s);
-    cn_prof_end(s);
+    if (!igemm_wgrad_slices(g, wgrad_tile(cfg), g_tune_wg_blocks, q.det, p)) {
+        p.ret = CN_EINVAL;
+        return p;
+    }
+    take(CN_WG_IGEMM, wgrad_family(cfg));
+    p.cfg = cfg;
+    sliced_grid(g, wgrad_tile(cfg), p);
+    p.zero = true;
+    if (q.det) {
+        p.det_floats = (size_t)p.splits * count;
+        p.sum = WG_SUM_PARTS;
+    }
+    return p;
+}
+
+// The launch check and the reduction that follows a launch: cn_sum_parts over the workspace's (or, in deterministic mode, the stream's)
+// partials, the K = 27 kernel's own sum, or nothing here where the slabs stay with the caller.
+int sum_conv_wgrad(const WgradPlan& p, int nparts, long count, int mode, float* gw, const float* ws, const float* det, int* parts_out,
+                   hipStream_t s) {
+    CN_LAUNCH_CHECK();
+    const int add = mode != CN_WGRAD_WRITE;
+    if (p.sum == WG_SUM_PARTS) return cn_sum_parts(det ? det : ws, gw, nparts, count, det ? 1 : add, 1.f, s);      // (det: gw was cleared or holds the sum so far)
+    if (p.sum == WG_SUM_C3) {
+        cn_c3_wgrad_reduce(ws, gw, nparts, (int)count, mode == CN_WGRAD_ADD, s);
+        CN_LAUNCH_CHECK();
+    }
+    if (p.sum == WG_SUM_CALLER) *parts_out = nparts;
+    return CN_OK;
+}
+
+// Performs the plan: zero pass, profile bracket, ONE launch, launch check, the reduction that follows.  A plan without a launch
+// returns its code before anything is enqueued.  mode: CN_WGRAD_WRITE / _ADD / _ZEROED (include/confignet_hip.h) -- a target known
+// to be zero is added to, except by the K = 27 route, which writes it.
+int run_conv_wgrad(const WgradPlan& p, const CnConvGeom& g, const WgradReq& q, const void* x, const void* gy, float* gw, int mode,
+                   float* ws, size_t ws_bytes, int* parts_out, hipStream_t s) {
+    if (parts_out) *parts_out = 0;
+    if (p.route == CN_WG_NONE) return p.ret;
+    CN_CHECK_ARG(mode == CN_WGRAD_WRITE || mode == CN_WGRAD_ADD || mode == CN_WGRAD_ZEROED, "filter gradient: mode %d", mode);
+    CN_CHECK_ARG(p.ws_floats == 0 || (ws && ws_bytes >= sizeof(float) * p.ws_floats), "filter gradient: workspace of %zu bytes, %zu needed",
+                 ws ? ws_bytes : (size_t)0, sizeof(float) * p.ws_floats);
+    CN_CHECK_ARG(p.sum != WG_SUM_CALLER || parts_out, "filter gradient: slabs left to a caller that takes none");
+    CN_CHECK_ARG(p.route != CN_WG_BF16 || (((uintptr_t)x | (uintptr_t)gy) & 15) == 0, "bf16 convolution needs 16-byte aligned tensors");
+    const long count = (long)g.k_d * g.k_h * g.k_w * g.cin * g.cout;
+    const int add = mode != CN_WGRAD_WRITE;
+    float* det = nullptr;
+    if (p.det_floats) {
+        det = cn_det_ws(s, p.det_floats);
+        if (!det) return CN_EINVAL;
+    }
+    if (p.zero && !add) {
+        if (int ez__ = cn_zero_async(gw, sizeof(float) * count, s)) return ez__;
+    }
+    if (p.family >= 0)
+        cn_prof_begin(s, p.route == CN_WG_C3 ? 2.0 * 27.0 * g.cout * (double)g.n * g.out_h * g.out_w : conv_flops(g),
+                      conv_bytes(g, q.x_dt == CN_BF16 ? 2.0 : 4.0, q.gy_dt == CN_BF16 ? 2.0 : 4.0, 4.0), p.family);
+    const dim3 grid(p.grid[0], p.grid[1], p.grid[2]);
+    int nparts = (int)p.splits, e = CN_OK;       // partials the reduction adds: row slices, or the workgroups of the C3 / THIN / TINY launch
+    switch (p.route) {
+        case CN_WG_C3:
+            e = cn_c3_wgrad(g, (const float*)x, gy, q.gy_dt, ws, p.tx, g.n * g.out_h * p.tx, nparts = p.grid[0], p.lds, s);
+            break;
+        case CN_WG_THIN:
+            cn_thin_wgrad(g, (const float*)x, (const float*)gy, ws, nparts = p.grid[0], p.lds, p.ty, p.tx, g.n * p.ty * p.tx, s);
+            break;
+        case CN_WG_TINY:
+            nparts = cn_tiny_wgrad(g, (const float*)x, (const float*)gy, gw, p.grid[0], det, s);
+            break;
+        case CN_WG_WGRAD2:
+            cn_wgrad2(p.cfg, p.stages, g, (const float*)x, (const float*)gy, p.splits > 1 ? ws : gw, p.splits > 1 ? count : 0, (int)p.rows,
+                      p.tx, p.ty, (int)p.splits, add, grid.x, s);
+            break;
+        case CN_WG_IGEMM:
+            cn_igemm_wgrad(p.cfg, g, (const float*)x, (const float*)gy, gw, (int)p.rows, det, p.tx, p.ty, (int)p.splits, grid, s);
+            break;
+        default:
+            cn_bf16_wgrad(p.cfg, g, x, gy, gw, (int)p.rows, p.tx, p.ty, (int)p.splits, grid, s);
+            break;
+    }
+    const bool sum_in_bracket = p.route != CN_WG_C3;      // (the K = 27 bracket has always closed in front of its reduction)
+    if (p.family >= 0 && !sum_in_bracket) cn_prof_end(s);
+    if (e == CN_OK) e = sum_conv_wgrad(p, nparts, count, mode, gw, ws, det, parts_out, s);
+    if (p.family >= 0 && sum_in_bracket) cn_prof_end(s);
     return e;
 }
 
-static bool wgrad2_takes(const CnConvGeom& g) {
-    // Every geometry the LDS-DMA kernel can take (round 6: with the slot layout and the XCD-aware slice plan it is at or ahead of
-    // the round-3 kernel -- split over rows, fp32 atomics -- on every shape of the iteration, profiles/round6_wgrad_shapes.txt).
-    // The round-3 kernel keeps the rest: channel counts that are no multiple of 4, K < 64, > 2 GiB operands.
-    const long Ktot = (long)g.k_d * g.k_h * g.k_w * g.cin;
-    return cn_wgrad2_ok(g) && Ktot >= 64;
+// argument checks, plan, run: the body of the filter-gradient entries below
+int conv_wgrad(const CnConvGeom* gp, const WgradReq& q, const void* x, const void* gy, float* gw, int mode, void* ws, size_t ws_bytes,
+               int* parts, void* stream) {
+    if (int e = check_geom(gp)) return e;
+    CN_CHECK_ARG(x && gy && gw, "NULL tensor");
+    return run_conv_wgrad(plan_conv_wgrad(*gp, q), *gp, q, x, gy, gw, mode, (float*)ws, ws_bytes, parts, (hipStream_t)stream);
+}
+
+}  // namespace
+
+// The atomic kernels alone (the from-RGB shapes, the row-split kernel): no workspace of the caller's.
+extern "C" int cn_conv_wgrad(const CnConvGeom* gp, const float* x, const float* gy, float* gw, int accumulate, void* stream) {
+    return conv_wgrad(gp, WgradReq{CN_F32, CN_F32, false, WG_ATOMIC}, x, gy, gw, accumulate ? CN_WGRAD_ADD : CN_WGRAD_WRITE, nullptr, 0, nullptr, stream);
 }
 
 // Workspace (bytes) that cn_conv_wgrad_ws needs for this geometry: room for the partial filters of its row splits; 0 = none.
 extern "C" size_t cn_conv_wgrad_workspace_bytes(const CnConvGeom* gp) {
-    if (!gp || check_geom(gp) != CN_OK || !wgrad2_takes(*gp)) return 0;
-    return sizeof(float) * cn_wgrad2_workspace_floats(*gp);
+    if (!gp || check_geom(gp) != CN_OK) return 0;
+    return sizeof(float) * plan_conv_wgrad(*gp, WgradReq{CN_F32, CN_F32, false, WG_FP32_GEMM}).ws_floats;
 }
 
-// Filter gradient with a CALLER-OWNED workspace (the caller owns all device memory): LDS-DMA main loop, row splits
-// through partial slabs in `workspace` + one ordered reduction -- no atomics on the tile, bit-reproducible (wgrad2.hip).
-// Geometries the new kernel does not take (channel counts that are no multiple of 4, K < 64, > 2 GiB operands) go to
-// cn_conv_wgrad and need no workspace.
-static int wgrad_ws_impl(const CnConvGeom* gp, const float* x, const float* gy, float* gw, int accumulate, void* workspace,
-                         size_t workspace_bytes, int* parts, void* stream) {
-    if (int e = check_geom(gp)) return e;
-    CN_CHECK_ARG(x && gy && gw, "NULL tensor");
-    if (parts) *parts = 0;
-    if (!wgrad2_takes(*gp)) return cn_conv_wgrad(gp, x, gy, gw, accumulate, stream);
-    const size_t need = sizeof(float) * cn_wgrad2_workspace_floats(*gp);
-    CN_CHECK_ARG(workspace_bytes >= need && (need == 0 || workspace), "cn_conv_wgrad_ws: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    hipStream_t s = (hipStream_t)stream;
-    cn_prof_begin(s, conv_flops(*gp), conv_bytes(*gp), cn_wgrad2_family(*gp));
-    const int e = cn_wgrad2(*gp, x, gy, gw, accumulate, (float*)workspace, s, parts);
-    cn_prof_end(s);
-    return e;
-}
-
+// Filter gradient with a CALLER-OWNED workspace (the caller owns all device memory): the LDS-DMA kernel where it takes
+// the geometry, else the atomic kernels, which need no workspace.
 extern "C" int cn_conv_wgrad_ws(const CnConvGeom* gp, const float* x, const float* gy, float* gw, int accumulate, void* workspace,
                                 size_t workspace_bytes, void* stream) {
-    return wgrad_ws_impl(gp, x, gy, gw, accumulate, workspace, workspace_bytes, nullptr, stream);
+    return conv_wgrad(gp, WgradReq{CN_F32, CN_F32, false, WG_FP32_GEMM}, x, gy, gw, accumulate ? CN_WGRAD_ADD : CN_WGRAD_WRITE, workspace,
+                      workspace_bytes, nullptr, stream);
 }
 
 // cn_conv_wgrad_ws that leaves the slabs to the caller (include/confignet_hip.h): *parts = 0 -> gw is complete
 extern "C" int cn_conv_wgrad_ws_slabs(const CnConvGeom* gp, const float* x, const float* gy, float* gw, int accumulate, void* workspace,
                                       size_t workspace_bytes, int* parts, void* stream) {
     CN_CHECK_ARG(parts, "cn_conv_wgrad_ws_slabs: parts is NULL");
-    return wgrad_ws_impl(gp, x, gy, gw, accumulate, workspace, workspace_bytes, parts, stream);
+    return conv_wgrad(gp, WgradReq{CN_F32, CN_F32, true, WG_FP32_GEMM}, x, gy, gw, accumulate ? CN_WGRAD_ADD : CN_WGRAD_WRITE, workspace,
+                      workspace_bytes, parts, stream);
+}
+
+extern "C" int cn_conv_wgrad_bf16(const CnConvGeom* gp, const uint16_t* x, const uint16_t* gy, float* gw, int accumulate,
+                                  void* stream) {
+    return conv_wgrad(gp, WgradReq{CN_BF16, CN_BF16, false, wg_bit(CN_WG_BF16)}, x, gy, gw, accumulate ? CN_WGRAD_ADD : CN_WGRAD_WRITE, nullptr, 0,
+                      nullptr, stream);
+}
+
+// Number of partial filters (27 x cout floats each) the caller provides as scratch.
+extern "C" int cn_conv_wgrad_c3_partials(void) { return CN_C3_WGRAD_PARTS; }
+
+// Filter gradient of a 3x3 convolution of a 3-channel fp32 image (g->cin == 3, stride 1 or 2, no dilation / upsample,
+// cout <= 64 and a multiple of 4); gy in fp32 or bf16 (gy_dt).  scratch: cn_conv_wgrad_c3_partials() * 27 * cout floats.  accumulate: add to gw.
+// Returns CN_EUNSUPPORTED (nothing launched) for other geometries.
+extern "C" int cn_conv_wgrad_c3(const CnConvGeom* gp, const float* x, const void* gy, int gy_dt, float* scratch, float* gw,
+                                int accumulate, void* stream) {
+    CN_CHECK_ARG(gp && x && gy && scratch && gw && (gy_dt == CN_F32 || gy_dt == CN_BF16), "conv_wgrad_c3: bad args");
+    return conv_wgrad(gp, WgradReq{CN_F32, gy_dt, false, wg_bit(CN_WG_C3)}, x, gy, gw, accumulate ? CN_WGRAD_ADD : CN_WGRAD_WRITE, scratch, SIZE_MAX,
+                      nullptr, stream);
+}
+
+extern "C" int cn_conv_wgrad_thin_partials(void) { return CN_THIN_WGRAD_PARTS; }
+
+// Filter gradient for cout <= 4 (thin_wgrad.hip).  scratch: cn_conv_wgrad_thin_partials() * taps * cin * cout floats.
+// accumulate: add to gw.  CN_EUNSUPPORTED (nothing launched) for every other geometry.
+extern "C" int cn_conv_wgrad_thin(const CnConvGeom* gp, const float* x, const float* gy, float* scratch, float* gw, int accumulate,
+                                  void* stream) {
+    CN_CHECK_ARG(scratch, "conv_wgrad_thin: NULL");
+    return conv_wgrad(gp, WgradReq{CN_F32, CN_F32, false, wg_bit(CN_WG_THIN)}, x, gy, gw, accumulate ? CN_WGRAD_ADD : CN_WGRAD_WRITE, scratch, SIZE_MAX,
+                      nullptr, stream);
+}
+
+// The routed filter gradient (include/confignet_hip.h): every route, the operands in the storage types the caller holds them in.
+extern "C" int cn_conv_wgrad_dt_workspace_bytes(const CnConvGeom* gp, int x_dt, int gy_dt, size_t* bytes) {
+    if (int e = check_geom(gp)) return e;
+    CN_CHECK_ARG(bytes, "cn_conv_wgrad_dt_workspace_bytes: bytes is NULL");
+    const WgradPlan p = plan_conv_wgrad(*gp, WgradReq{x_dt, gy_dt, false, WG_ALL});
+    *bytes = sizeof(float) * p.ws_floats;
+    return p.ret;
+}
+
+extern "C" int cn_conv_wgrad_dt(const CnConvGeom* gp, const void* x, int x_dt, const void* gy, int gy_dt, float* gw, int mode, void* workspace,
+                                size_t workspace_bytes, int* parts, void* stream) {
+    return conv_wgrad(gp, WgradReq{x_dt, gy_dt, parts != nullptr, WG_ALL}, x, gy, gw, mode, workspace, workspace_bytes, parts, stream);
+}
+
+// Diagnostic (include/confignet_hip.h): the launch a filter-gradient request WOULD get -- needs no device, enqueues nothing.
+extern "C" int cn_conv_wgrad_plan(const CnConvGeom* gp, int x_dt, int gy_dt, int caller_slabs, unsigned routes, int det, long long out[12]) {
+    if (int e = check_geom(gp)) return e;
+    CN_CHECK_ARG(out, "cn_conv_wgrad_plan: out is NULL");
+    const WgradPlan p = plan_conv_wgrad(*gp, WgradReq{x_dt, gy_dt, caller_slabs != 0, routes, det < 0 ? cn_det() != 0 : det != 0});
+    const long long v[12] = {p.route, p.cfg, p.splits, p.rows, p.family, p.grid[0], p.grid[1], p.grid[2], (long long)p.ws_floats, p.zero, p.sum, p.stages};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return p.ret;
 }
 
 // Tuning hook of the forward / data-gradient main loop (include/confignet_hip.h): loop = 1 / 0 forces the LDS-DMA loop on / off for
@@ -471,18 +774,17 @@ extern "C" int cn_conv_loop_select(int loop, int kb, int ns, int np) {
                  "cn_conv_loop_select: bad argument");
     g_fwd2_sel = loop;
     cn_fwd2_tune(kb, ns, np);
-    cn_wgrad2_stages(ns);
+    g_tune_wg2_ns = ns;
     return CN_OK;
 }
 
 // Tuning hook (scripts/conv_sweep.py): force the tile configuration (0 = 128x128, 1 = 128x64, 2 = 64x64, 3 = 128x32, 4 = 128x96;
-// -1 = heuristic), the split-K factor of cn_conv_fwd / cn_conv_dgrad (0 = heuristic) and the workgroup target of cn_conv_wgrad
-// (0 = default).  Process-wide; not for production use.
+// -1 = heuristic), the split-K factor of cn_conv_fwd / cn_conv_dgrad (0 = heuristic) and the workgroup target of the filter gradient
+// (0 = default).  Of the filter-gradient kernels the LDS-DMA one takes the tile (0 / 4 / 2 / 3, 5 = 256x64) and the target, the atomic
+// one the target (plan_conv_wgrad).  Process-wide; not for production use.
 extern "C" int cn_conv_tune(int cfg, int splits, long wg_blocks) {
     g_tune_cfg = cfg;
     g_tune_splits = splits;
     g_tune_wg_blocks = wg_blocks;
-    // the same hook steers cn_conv_wgrad_ws: tile 0 / 4 / 2 / 3 -> 128x128 / 128x96 / 64x64 / 128x32, wg_blocks = workgroup target
-    cn_wgrad2_tune(cfg == 0 ? 0 : cfg == 4 ? 1 : cfg == 2 ? 2 : cfg == 3 ? 3 : cfg == 5 ? 4 : -1, wg_blocks);
     return CN_OK;
 }

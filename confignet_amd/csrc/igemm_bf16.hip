@@ -455,43 +455,6 @@ int conv_bf16(const CnConvGeom& g, int flip, const bf16_t* x, const bf16_t* wb, 
     return e;
 }
 
-template <int WM, int WN, int TM, int TN>
-int launch_bf16_wgrad(const CnConvGeom& g, const bf16_t* x, const bf16_t* gy, float* gw, hipStream_t s) {
-    constexpr int BMt = 32 * WM * TM, BNt = 32 * WN * TN;
-    const long M = (long)g.n * g.out_d * g.out_h * g.out_w;
-    const long Ktot = (long)g.k_d * g.k_h * g.k_w * g.cin;
-    const long tiles = (long)cn_cdiv(Ktot, BMt) * cn_cdiv(g.cout, BNt);
-    // Row slices (round-5 sweep, profiles/round5_bf16_wgrad_splits.txt).  What the sweep showed: (1) a slice shorter than ~512
-    // rows is mostly prologue + the tile's atomic adds; (2) one workgroup more than the CUs hold at once costs a whole extra
-    // round -- the kernels hold 3 (128 x 128), 4 (128 x 96) or 5 workgroups per CU -- and the narrow tiles like two rounds;
-    // (3) with the XCD order a slice count that is not a multiple of 8 leaves XCDs with one slice more than others.
-    constexpr long min_rows = 512;
-    long splits;
-    {
-        const long per_cu = BMt * BNt >= 128 * 128 ? 3 : BMt * BNt >= 128 * 96 ? 4 : 5;
-        const long target = 256 * per_cu * (BNt >= 96 ? 1 : 2);
-        splits = target / tiles;
-        if (splits > M / min_rows) splits = M / min_rows;
-        const long fill = std::min<long>(M / 256, (256 + tiles - 1) / tiles);        // ... but at least one workgroup per CU
-        if (splits < fill) splits = fill;
-        if (splits >= 16) splits &= ~7L;
-        if (splits < 1) splits = 1;
-    }
-    long rows = (M + splits - 1) / splits;
-    if (rows < 256) rows = std::min<long>(256, (M + KS - 1) / KS * KS);
-    rows = (rows + KS - 1) / KS * KS;
-    splits = (M + rows - 1) / rows;
-    dim3 grid(cn_cdiv(Ktot, BMt), cn_cdiv(g.cout, BNt), (unsigned)splits);
-    int tx = 0, ty = 0;
-    if (grid.x * grid.y > 1 && splits >= 16) {
-        tx = (int)grid.x; ty = (int)grid.y;
-        grid = dim3((unsigned)(cn_cdiv(splits, 8) * 8 * tx * ty), 1, 1);
-    }
-    hipLaunchKernelGGL((igemm_bf16_wgrad_tr_kernel<WM, WN, TM, TN>), grid, dim3(256), 0, s, g, x, gy, gw, (int)rows, tx, ty, (int)splits);
-    CN_LAUNCH_CHECK();
-    return CN_OK;
-}
-
 }  // namespace
 
 extern "C" int cn_conv_weight_prep_bf16(const float* w, uint16_t* wf, uint16_t* wd, int taps, int cin, int cout, void* stream) {
@@ -520,26 +483,17 @@ extern "C" int cn_conv_dgrad_bf16(const CnConvGeom* gp, const uint16_t* gy, cons
     return conv_bf16(d, 1, gy, wd, nullptr, gu, CN_ACT_NONE, 0.f, (hipStream_t)stream);
 }
 
-extern "C" int cn_conv_wgrad_bf16(const CnConvGeom* gp, const uint16_t* x, const uint16_t* gy, float* gw, int accumulate,
-                                  void* stream) {
-    if (int e = check_geom(gp)) return e;
-    CN_CHECK_ARG(x && gy && gw, "NULL tensor");
-    const CnConvGeom g = *gp;
-    if (g.cin % 8 || g.cout % 8) return CN_EUNSUPPORTED;
-    CN_CHECK_ARG((((uintptr_t)x | (uintptr_t)gy) & 15) == 0, "bf16 convolution needs 16-byte aligned tensors");
-    hipStream_t s = (hipStream_t)stream;
-    const long Ktot = (long)g.k_d * g.k_h * g.k_w * g.cin;
-    if (!accumulate) {
-        if (int ez__ = cn_zero_async(gw, sizeof(float) * Ktot * g.cout, s)) return ez__;
+// One launch of the bf16 filter gradient (fp32 atomics on the tile) on tile cfg with the slices, rows per slice and grid of the plan
+// (conv_dispatch.hip: bf16_wgrad_slices; tx / ty != 0: the XCD-ordered 1-D grid)
+void cn_bf16_wgrad(int cfg, const CnConvGeom& g, const void* x, const void* gy, float* gw, int rows, int tx, int ty, int splits, dim3 grid,
+                   hipStream_t s) {
+#define BW(WM, WN, TM, TN) hipLaunchKernelGGL((igemm_bf16_wgrad_tr_kernel<WM, WN, TM, TN>), grid, dim3(256), 0, s, g, (const bf16_t*)x, \
+                                              (const bf16_t*)gy, gw, rows, tx, ty, splits)
+    switch (cfg) {
+        case 3: BW(4, 1, 1, 1); break;       // 128 (tap,ci) x 32 co
+        case 4: BW(4, 1, 1, 3); break;       // 128 x 96
+        case 0: BW(2, 2, 2, 2); break;       // 128 x 128
+        default: BW(2, 2, 1, 1); break;      // 64 x 64
     }
-    cn_prof_begin(s, conv_flops(g), conv_bytes(g, 2.0, 2.0, 4.0), CN_FAM_BF16_WGRAD);
-    int e;
-    switch (wgrad_tile_cfg(g)) {
-        case 3: e = launch_bf16_wgrad<4, 1, 1, 1>(g, x, gy, gw, s); break;       // 128 (tap,ci) x 32 co
-        case 4: e = launch_bf16_wgrad<4, 1, 1, 3>(g, x, gy, gw, s); break;       // 128 x 96
-        case 0: e = launch_bf16_wgrad<2, 2, 2, 2>(g, x, gy, gw, s); break;       // 128 x 128
-        default: e = launch_bf16_wgrad<2, 2, 1, 1>(g, x, gy, gw, s); break;      // 64 x 64
-    }
-    cn_prof_end(s);
-    return e;
+#undef BW
 }

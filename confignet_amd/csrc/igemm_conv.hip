@@ -600,45 +600,15 @@ int launch_fwd(const CnConvGeom& g, bool vec, int par, int splits, const float* 
 }
 
 template <int WM, int WN, int TM, int TN>
-int launch_wgrad(const CnConvGeom& g, const float* x, const float* gy, float* gw, long wg_target, hipStream_t s) {
-    constexpr int BMt = 32 * WM * TM, BNt = 32 * WN * TN;
-    const long M = (long)g.n * g.out_d * g.out_h * g.out_w;
-    const long Ktot = (long)g.k_d * g.k_h * g.k_w * g.cin;
-    const long tiles = (long)cn_cdiv(Ktot, BMt) * cn_cdiv(g.cout, BNt);
-    const long wg_blocks = wg_target > 0 ? wg_target : 2048;   // sweep 256..4096: flat from 1536 up
-    long splits = (wg_blocks + tiles - 1) / tiles;
-    float* parts = nullptr;
-    if (cn_det()) {
-        // deterministic mode: per-split partial filters in the stream's workspace, added in split order by a second launch
-        // (every split of every tile writes its whole slab region: no clearing).  As many splits as the workspace holds.
-        const long cap = (long)(CN_DET_WS_FLOATS / ((size_t)Ktot * g.cout));
-        CN_CHECK_ARG(cap >= 1, "deterministic filter gradient: %ld x %d filter does not fit the workspace", Ktot, g.cout);
-        if (splits > cap) splits = cap;
-    }
-    long rows = (M + splits - 1) / splits;
-    if (rows < 256) rows = 256;
-    rows = (rows + BK - 1) / BK * BK;
-    splits = (M + rows - 1) / rows;
-    if (cn_det()) {
-        parts = cn_det_ws(s, (size_t)splits * Ktot * g.cout);
-        if (!parts) return CN_EINVAL;
-    }
-    dim3 grid(cn_cdiv(Ktot, BMt), cn_cdiv(g.cout, BNt), (unsigned)splits);
-    int tx = 0, ty = 0;
-    if (grid.x * grid.y > 1 && splits >= 16) {
-        tx = (int)grid.x; ty = (int)grid.y;
-        grid = dim3((unsigned)(cn_cdiv(splits, 8) * 8 * tx * ty), 1, 1);
-    }
+void launch_wgrad(const CnConvGeom& g, const float* x, const float* gy, float* gw, int rows, float* parts, int tx, int ty, int splits,
+                  dim3 grid, hipStream_t s) {
     const bool avec = g.cin % 4 == 0, bvec = g.cout % 4 == 0;
-#define WG(A, B) hipLaunchKernelGGL((igemm_wgrad_kernel<WM, WN, TM, TN, A, B>), grid, dim3(256), 0, s, g, x, gy, gw, (int)rows, parts, tx, ty, (int)splits)
+#define WG(A, B) hipLaunchKernelGGL((igemm_wgrad_kernel<WM, WN, TM, TN, A, B>), grid, dim3(256), 0, s, g, x, gy, gw, rows, parts, tx, ty, splits)
     if (avec && bvec) WG(true, true);
     else if (avec) WG(true, false);
     else if (bvec) WG(false, true);
     else WG(false, false);
 #undef WG
-    CN_LAUNCH_CHECK();
-    if (parts) return cn_sum_parts(parts, gw, (int)splits, Ktot * g.cout, 1, 1.f, s);      // gw was cleared (or holds the sum so far)
-    return CN_OK;
 }
 
 }  // namespace
@@ -670,36 +640,27 @@ int cn_igemm_fwd_thin(const CnConvGeom& g, const float* x, const float* w, const
     return CN_OK;
 }
 
-int cn_igemm_wgrad(int cfg, const CnConvGeom& g, const float* x, const float* gy, float* gw, long wg_target, hipStream_t s) {
+// One launch of the row-split filter gradient on tile cfg with the slices, rows per slice and grid of the plan (tx / ty != 0: the
+// XCD-ordered 1-D grid); parts: per-slice partial filters instead of atomics (deterministic mode)
+void cn_igemm_wgrad(int cfg, const CnConvGeom& g, const float* x, const float* gy, float* gw, int rows, float* parts, int tx, int ty,
+                    int splits, dim3 grid, hipStream_t s) {
     switch (cfg) {
-        case 3: return launch_wgrad<4, 1, 1, 1>(g, x, gy, gw, wg_target, s);       // 128 (tap,ci) x 32 co
-        case 4: return launch_wgrad<4, 1, 1, 3>(g, x, gy, gw, wg_target, s);       // 128 x 96: cout 96 / 192 without column padding
-        case 0: return launch_wgrad<2, 2, 2, 2>(g, x, gy, gw, wg_target, s);       // 128 x 128
-        default: return launch_wgrad<2, 2, 1, 1>(g, x, gy, gw, wg_target, s);      // 64 x 64
+        case 3: return launch_wgrad<4, 1, 1, 1>(g, x, gy, gw, rows, parts, tx, ty, splits, grid, s);       // 128 (tap,ci) x 32 co
+        case 4: return launch_wgrad<4, 1, 1, 3>(g, x, gy, gw, rows, parts, tx, ty, splits, grid, s);       // 128 x 96: cout 96 / 192 without column padding
+        case 0: return launch_wgrad<2, 2, 2, 2>(g, x, gy, gw, rows, parts, tx, ty, splits, grid, s);       // 128 x 128
+        default: return launch_wgrad<2, 2, 1, 1>(g, x, gy, gw, rows, parts, tx, ty, splits, grid, s);      // 64 x 64
     }
 }
 
-// filter gradient of the from-RGB shapes (1x1, cin and cout <= 4); CN_EUNSUPPORTED (nothing launched) for every other geometry
-int cn_tiny_wgrad(const CnConvGeom& g, const float* x, const float* gy, float* gw, hipStream_t s) {
-    const long Ktot = (long)g.k_d * g.k_h * g.k_w * g.cin;
-    if (!(Ktot <= 4 && g.cout <= 4 && g.k_d * g.k_h * g.k_w == 1 && g.s_h == 1 && g.s_w == 1 && g.s_d == 1 && !g.up &&
-          g.p_h == 0 && g.p_w == 0 && g.p_d == 0))
-        return CN_EUNSUPPORTED;
+// filter gradient of the from-RGB shapes (1x1, cin and cout <= 4) on `blocks` workgroups; parts: per-workgroup partials instead of
+// atomics.  Returns the workgroups launched (the 3 -> 3 kernel for 16-byte aligned operands runs on at most 512).
+int cn_tiny_wgrad(const CnConvGeom& g, const float* x, const float* gy, float* gw, int blocks, float* parts, hipStream_t s) {
     const long M = (long)g.n * g.out_d * g.out_h * g.out_w;
-    const int blocks = (int)(cn_cdiv(M, 256) > 1024 ? 1024 : cn_cdiv(M, 256));
-    float* parts = nullptr;
-    if (cn_det()) {                  // deterministic mode: per-workgroup partials, added in workgroup order
-        parts = cn_det_ws(s, (size_t)blocks * 16);
-        if (!parts) return CN_EINVAL;
-    }
-    int nb = blocks;
     if (g.cin == 3 && g.cout == 3 && (((uintptr_t)x | (uintptr_t)gy) & 15) == 0) {
-        nb = blocks > 512 ? 512 : blocks;
+        const int nb = blocks > 512 ? 512 : blocks;
         hipLaunchKernelGGL(tiny_wgrad_3x3_kernel, dim3(nb), dim3(256), 0, s, x, gy, gw, M, parts);
-    } else {
-        hipLaunchKernelGGL(tiny_wgrad_1x1_kernel, dim3(blocks), dim3(256), 0, s, x, gy, gw, M, g.cin, g.cout, parts);
+        return nb;
     }
-    CN_LAUNCH_CHECK();
-    if (parts) return cn_sum_parts(parts, gw, nb, (long)g.cin * g.cout, 1, 1.f, s);
-    return CN_OK;
+    hipLaunchKernelGGL(tiny_wgrad_1x1_kernel, dim3(blocks), dim3(256), 0, s, x, gy, gw, M, g.cin, g.cout, parts);
+    return blocks;
 }

@@ -10,8 +10,7 @@
 
 namespace {
 
-constexpr int TH = 8, TW = 32;            // output pixels of a tile
-constexpr int NWG = 512;                  // workgroups = partial filters
+constexpr int TH = CN_THIN_WGRAD_TH, TW = CN_THIN_WGRAD_TW;            // output pixels of a tile
 
 template <int CO>
 __global__ __launch_bounds__(256) void thin_wgrad_kernel(CnConvGeom g, const float* __restrict__ X, const float* __restrict__ GY,
@@ -101,29 +100,9 @@ __global__ __launch_bounds__(256) void thin_wgrad_kernel(CnConvGeom g, const flo
 
 }  // namespace
 
-extern "C" int cn_conv_wgrad_thin_partials(void) { return NWG; }
-
-// Filter gradient for cout <= 4 (see the header of this file).  scratch: cn_conv_wgrad_thin_partials() * taps * cin * cout floats.
-// accumulate: add to gw.  CN_EUNSUPPORTED (nothing launched) for every other geometry.
-extern "C" int cn_conv_wgrad_thin(const CnConvGeom* gp, const float* x, const float* gy, float* scratch, float* gw, int accumulate,
-                                  void* stream) {
-    if (int e = check_geom(gp)) return e;
-    const CnConvGeom g = *gp;
-    const int T = g.k_h * g.k_w;
-    if (g.nd != 2 || g.cout > 4 || g.cin % 4 || g.cin > 64 || g.s_h != 1 || g.s_w != 1 || g.dl_h != 1 || g.dl_w != 1 || T > 16 ||
-        T * (g.cin / 4) > 256 || g.cin < 8)
-        return CN_EUNSUPPORTED;
-    CN_CHECK_ARG(x && gy && scratch && gw, "conv_wgrad_thin: NULL");
-    hipStream_t s = (hipStream_t)stream;
-    const int tiles_y = cn_cdiv(g.out_h, TH), tiles_x = cn_cdiv(g.out_w, TW);
-    const int ntiles = g.n * tiles_y * tiles_x;
-    const int nwg = ntiles < NWG ? ntiles : NWG;
-    const int PH0 = ((TH + g.k_h - 1) >> g.up) + 2, PW0 = ((TW + g.k_w - 1) >> g.up) + 2;
-    size_t lds = sizeof(float) * ((size_t)PH0 * PW0 * g.cin + TH * TW * 4);
-    const size_t red = sizeof(float) * 256 * 4 * g.cout;
-    if (lds < red) lds = red;
-    if (lds > 64 * 1024) return CN_EUNSUPPORTED;
-    const long count = (long)T * g.cin * g.cout;
+// One launch on nwg workgroups (each writes one partial filter to scratch) with the numbers of the plan (conv_dispatch.hip)
+void cn_thin_wgrad(const CnConvGeom& g, const float* x, const float* gy, float* scratch, int nwg, size_t lds, int tiles_y, int tiles_x,
+                   int ntiles, hipStream_t s) {
 #define TW_LAUNCH(CO_) hipLaunchKernelGGL((thin_wgrad_kernel<CO_>), dim3(nwg), dim3(256), lds, s, g, x, gy, scratch, tiles_y, tiles_x, ntiles)
     switch (g.cout) {
         case 1: TW_LAUNCH(1); break;
@@ -132,6 +111,4 @@ extern "C" int cn_conv_wgrad_thin(const CnConvGeom* gp, const float* x, const fl
         default: TW_LAUNCH(4); break;
     }
 #undef TW_LAUNCH
-    CN_LAUNCH_CHECK();
-    return cn_sum_parts(scratch, gw, nwg, count, accumulate, 1.f, s);
 }

@@ -335,24 +335,15 @@ __global__ __launch_bounds__(256) void wgrad2_kernel(CnConvGeom g, const float* 
     wgrad2_body<WM, WN, TM, TN, KB, NS>(g, X, GY, out, slab_stride, rows_per_split, tiles_x, tiles_y, nsplits, accumulate);
 }
 
-struct Wg2Plan {
-    int cfg;          // 0: 128x128, 1: 128x96, 2: 64x64, 3: 128x32, 4: 256x64
-    int bi, bn, kb;
-    long tiles_x, tiles_y, splits, rows;
-};
-
-long g_wg2_target = 0;     // cn_conv_tune(wg_blocks): workgroup target of the split (0 = the model below)
-int g_wg2_cfg = -1;        // cn_conv_tune(cfg): forced tile
-int g_wg2_ns = 0;          // cn_conv_loop_select(ns): forced stage count
-
-// The tiles: rows of (tap, ci) x output channels, reduction rows per stage, and the share of the matrix pipes a CU sustains on the
-// tile with one / with two workgroups resident (fitted to the per-shape sweep of round 6, profiles/round6_wgrad_sweep_points.txt).
+// The tiles (cfg in the implicit-GEMM numbering of cn_conv_tune; 5 = 256 x 64): rows of (tap, ci) x output channels, reduction rows
+// per stage, and the share of the matrix pipes a CU sustains on the tile with one / with two workgroups resident (fitted to the
+// per-shape sweep of round 6, profiles/round6_wgrad_sweep_points.txt).
 struct Wg2Tile {
     int cfg, bi, bn, kb;
     double e1, e2;
 };
-const Wg2Tile WG2_TILES[5] = {{0, 128, 128, 16, 0.72, 0.84}, {1, 128, 96, 16, 0.62, 0.72}, {2, 64, 64, 32, 0.50, 0.56},
-                              {3, 128, 32, 32, 0.38, 0.42}, {4, 256, 64, 16, 0.55, 0.63}};
+const Wg2Tile WG2_TILES[5] = {{0, 128, 128, 16, 0.72, 0.84}, {4, 128, 96, 16, 0.62, 0.72}, {2, 64, 64, 32, 0.50, 0.56},
+                              {3, 128, 32, 32, 0.38, 0.42}, {5, 256, 64, 16, 0.55, 0.63}};
 
 // Estimated duration (us) of the launch + the slab reduction for `s` row slices on tile t.  Workgroups of one slice share an XCD
 // (slices dealt round-robin to the 8 XCDs, 32 CUs each, two workgroups resident per CU): the launch lasts as long as the XCD with
@@ -376,15 +367,20 @@ double wg2_cost(const Wg2Tile& t, long M, long Ktot, int cout, long s, long& row
     return us;
 }
 
-Wg2Plan wg2_plan(const CnConvGeom& g) {
+}  // namespace
+
+// Tile and row slices of the launch (common.h; conv_dispatch.hip: plan_conv_wgrad asks once per call).  forced: a tile of WG2_TILES
+// or -1 = the tiles the shape admits; target > 0: the slice count from that workgroup target instead of the model's best.  Some tile
+// is always considered (a forced one as it is; else 128 x 32 up to 32 output channels and 64 x 64 above), so the plan is always set.
+Wg2Plan cn_wgrad2_plan(const CnConvGeom& g, int forced, long target) {
     const long M = (long)g.n * g.out_d * g.out_h * g.out_w;
     const long Ktot = (long)g.k_d * g.k_h * g.k_w * g.cin;
     Wg2Plan p{};
     double best = -1.0;
     for (const Wg2Tile& t : WG2_TILES) {
-        if (g_wg2_cfg >= 0 ? t.cfg != g_wg2_cfg
-                           : ((t.cfg == 3) != (g.cout <= 32) || (t.cfg == 1 && g.cout % 96 != 0) || (t.cfg == 0 && g.cout < 96) ||
-                              (t.cfg == 4 && (g.cout % 64 != 0 || Ktot < 256)) || (t.cfg != 2 && t.cfg != 3 && Ktot < 128)))
+        if (forced >= 0 ? t.cfg != forced
+                        : ((t.cfg == 3) != (g.cout <= 32) || (t.cfg == 4 && g.cout % 96 != 0) || (t.cfg == 0 && g.cout < 96) ||
+                           (t.cfg == 5 && (g.cout % 64 != 0 || Ktot < 256)) || (t.cfg != 2 && t.cfg != 3 && Ktot < 128)))
             continue;
         const long tiles = (long)cn_cdiv(Ktot, t.bi) * cn_cdiv(g.cout, t.bn);
         const long max_splits = cn_cdiv(M, 4 * t.kb);                 // a workgroup is at least 4 K steps long
@@ -395,28 +391,20 @@ Wg2Plan wg2_plan(const CnConvGeom& g) {
             const double us = wg2_cost(t, M, Ktot, g.cout, s_, rows, splits);
             if (best < 0.0 || us < best) {
                 best = us;
-                p.cfg = t.cfg; p.bi = t.bi; p.bn = t.bn; p.kb = t.kb;
+                p.cfg = t.cfg;
                 p.tiles_x = cn_cdiv(Ktot, t.bi); p.tiles_y = cn_cdiv(g.cout, t.bn);
                 p.rows = rows; p.splits = splits;
             }
         };
-        if (g_wg2_target > 0) {
-            consider(tiles >= g_wg2_target ? 1 : (g_wg2_target + tiles / 2) / tiles);
+        if (target > 0) {
+            consider(tiles >= target ? 1 : (target + tiles / 2) / tiles);
         } else {
             for (long s_ = 1; s_ < 8 && s_ <= max_splits; ++s_) consider(s_);
             for (long s_ = 8; s_ <= max_splits && s_ <= 1024; s_ += 8) consider(s_);
         }
     }
-    if (best < 0.0) {          // (a forced tile that the shape cannot use: the 64 x 64 tile takes everything)
-        const int keep = g_wg2_cfg;
-        g_wg2_cfg = 2;
-        p = wg2_plan(g);
-        g_wg2_cfg = keep;
-    }
     return p;
 }
-
-}  // namespace
 
 bool cn_wgrad2_ok(const CnConvGeom& g) {
     const double xb = (double)g.n * g.in_d * g.in_h * g.in_w * g.cin * 4.0;
@@ -427,54 +415,20 @@ bool cn_wgrad2_ok(const CnConvGeom& g) {
            g.dl_d == 1 && g.dl_h == 1 && g.dl_w == 1 && sd < 8388608.0 && rows < 8388608.0 && g.cout < 8388608;
 }
 
-size_t cn_wgrad2_workspace_floats(const CnConvGeom& g) {
-    if (!cn_wgrad2_ok(g)) return 0;
-    const Wg2Plan p = wg2_plan(g);
-    const long Ktot = (long)g.k_d * g.k_h * g.k_w * g.cin;
-    return p.splits > 1 ? (size_t)p.splits * Ktot * g.cout : 0;
-}
-
-void cn_wgrad2_tune(int cfg, long wg_target) {
-    g_wg2_cfg = cfg;
-    g_wg2_target = wg_target;
-}
-
-void cn_wgrad2_stages(int ns) { g_wg2_ns = ns; }     // cn_conv_loop_select: 0 = default, 3 / 4 forced
-
-int cn_wgrad2_family(const CnConvGeom& g) {
-    const Wg2Plan p = wg2_plan(g);
-    return p.cfg == 0 ? CN_FAM_WGRAD_128x128 : p.cfg == 1 ? CN_FAM_WGRAD_128x96 : p.cfg == 2 ? CN_FAM_WGRAD_64x64 : p.cfg == 4 ? CN_FAM_WGRAD_256x64 : CN_FAM_WGRAD_128x32;
-}
-
-// gw (+)= filter gradient.  ws: at least cn_wgrad2_workspace_floats(g) floats (may be NULL when that is 0).
-// parts_out: NULL = add the slabs here (second launch); else the caller does: *parts_out = slabs written (0: gw is complete).
-int cn_wgrad2(const CnConvGeom& g, const float* x, const float* gy, float* gw, int accumulate, float* ws, hipStream_t s, int* parts_out) {
-    const Wg2Plan p = wg2_plan(g);
-    const long Ktot = (long)g.k_d * g.k_h * g.k_w * g.cin;
-    const long count = Ktot * g.cout;
-    CN_CHECK_ARG(p.splits == 1 || ws, "filter gradient: %ld row splits need a workspace of %ld floats", p.splits, p.splits * count);
-    const long ntile = p.tiles_x * p.tiles_y;
-    dim3 grid((unsigned)((p.splits >= 8 ? cn_cdiv(p.splits, 8) * 8 : p.splits) * ntile));
-    float* out = p.splits > 1 ? ws : gw;
-    const long stride = p.splits > 1 ? count : 0;
-#define WG2(WM, WN, TM, TN, KB_, NS_) hipLaunchKernelGGL((wgrad2_kernel<WM, WN, TM, TN, KB_, NS_>), grid, dim3(256), 0, s, g, x, gy, out, stride, \
-                                                          (int)p.rows, (int)p.tiles_x, (int)p.tiles_y, (int)p.splits, accumulate)
-    const int ns = g_wg2_ns ? g_wg2_ns : 4;
+// One launch of tile cfg with ns stages (the 128 x 32 tile always has three).  slab_stride != 0: slice z stores its partial filter at
+// out + z * slab_stride; else out is the filter gradient itself, stored or (accumulate) added to.
+void cn_wgrad2(int cfg, int ns, const CnConvGeom& g, const float* x, const float* gy, float* out, long slab_stride, int rows, int tiles_x,
+               int tiles_y, int splits, int accumulate, unsigned grid, hipStream_t s) {
+#define WG2(WM, WN, TM, TN, KB_, NS_) hipLaunchKernelGGL((wgrad2_kernel<WM, WN, TM, TN, KB_, NS_>), dim3(grid), dim3(256), 0, s, g, x, gy, out, slab_stride, \
+                                                          rows, tiles_x, tiles_y, splits, accumulate)
 #define WG2N(WM, WN, TM, TN, KB_) do { if (ns == 3) WG2(WM, WN, TM, TN, KB_, 3); else WG2(WM, WN, TM, TN, KB_, 4); } while (0)
-    switch (p.cfg) {
+    switch (cfg) {
         case 0: WG2N(2, 2, 2, 2, 16); break;
-        case 1: WG2N(4, 1, 1, 3, 16); break;
+        case 4: WG2N(4, 1, 1, 3, 16); break;
         case 2: WG2N(2, 2, 1, 1, 32); break;
-        case 4: WG2N(4, 1, 2, 2, 16); break;
+        case 5: WG2N(4, 1, 2, 2, 16); break;
         default: WG2(4, 1, 1, 1, 32, 3); break;
     }
 #undef WG2N
 #undef WG2
-    CN_LAUNCH_CHECK();
-    if (parts_out) {
-        *parts_out = p.splits > 1 ? (int)p.splits : 0;
-        return CN_OK;
-    }
-    if (p.splits > 1) return cn_sum_parts(ws, gw, (int)p.splits, count, accumulate, 1.f, s);
-    return CN_OK;
 }

@@ -521,66 +521,43 @@ def conv_dgrad_res(gy, w, g, res):
 
 
 DGRAD_FROM_W = True
-THIN_WGRAD = True
-C3_WGRAD = True
 MIXED_FIRST_LAYERS = True      # bf16 path: first-layer kernels that read / write both storage types
-_C3_PARTS = []
-
-
-def _c3_partials():
-    if not _C3_PARTS:
-        _C3_PARTS.append(int(lib.cn_conv_wgrad_c3_partials()))
-    return _C3_PARTS[0]
+WGRAD_WRITE, WGRAD_ADD, WGRAD_ZEROED = 0, 1, 2      # include/confignet_hip.h: CN_WGRAD_*
 
 
 def conv_wgrad(x, gy, g, w_shape, out=None, accumulate=True, defer=True, ws=None):
     """out: ADD the filter gradient to this tensor (a slot of a gradient arena, see grad_sink) instead of returning a new one;
     out with accumulate=False: WRITE it there (an uninitialised scratch the caller owns: the folded ResNet-50's packed gradients).
     defer=False: complete in `out` when this returns, also inside a grad_sink (no slab reduction left to its join).
-    ws: the caller's own fp32 workspace for cn_conv_wgrad_ws (at least cn_conv_wgrad_workspace_bytes(g)) instead of a fresh one."""
-    gw = out if out is not None else zero_pool_alloc(w_shape, x.device)
-    pre = gw is not None and (accumulate or out is None)
-    if gw is None:
-        gw = torch.empty(w_shape, device=x.device, dtype=torch.float32)
-    if C3_WGRAD and g.nd == 2 and g.cin == 3 and g.k_h == 3 and g.k_w == 3 and g.s_h == g.s_w and g.s_h in (1, 2) \
-            and g.dl_h == 1 and g.dl_w == 1 and g.up == 0 and g.cout <= 64 and g.cout % 4 == 0 and gy.dtype in (torch.float32, torch.bfloat16):
-        # K = 27 first layers: staged-tile kernel without atomics (the generic split-over-rows kernel runs them at 10 TFLOP/s)
-        x, gy = _c(f32(x)), _c(gy)
-        scratch = torch.empty(_c3_partials() * 27 * g.cout, device=x.device, dtype=torch.float32)
-        check(lib.cn_conv_wgrad_c3(ctypes.byref(g), _ptr(x), _ptr(gy), _dt(gy), _ptr(scratch), _fptr(gw), int(out is not None and accumulate), _stream()),
-              "cn_conv_wgrad_c3")
-        return gw
-    if THIN_WGRAD and g.nd == 2 and g.cout <= 4 and 8 <= g.cin <= 64 and g.cin % 4 == 0 and g.s_h == 1 and g.s_w == 1:
-        # thin output (map_final): staged-tile VALU kernel with ordered partial sums (the implicit-GEMM kernel runs it at 6 TFLOP/s)
-        x32, gy32 = _c(f32(x)), _c(f32(gy))
-        taps = g.k_h * g.k_w
-        scratch = torch.empty(int(lib.cn_conv_wgrad_thin_partials()) * taps * g.cin * g.cout, device=x.device, dtype=torch.float32)
-        rc = lib.cn_conv_wgrad_thin(ctypes.byref(g), _ptr(x32), _ptr(gy32), _ptr(scratch), _fptr(gw), int(pre), _stream())
-        if rc == 0:
-            return gw
-        if rc != CN_EUNSUPPORTED:
-            check(rc, "cn_conv_wgrad_thin")
-    if _bf16_conv_ok(g):
-        x, gy = cast(x, torch.bfloat16), cast(gy, torch.bfloat16)
-        check(lib.cn_conv_wgrad_bf16(ctypes.byref(g), _ptr(x), _ptr(gy), _fptr(gw), int(pre), _stream()), "cn_conv_wgrad_bf16")
-        return gw
-    x, gy = f32(x), f32(gy)
-    # caller-owned workspace for the partial filters of the kernel's row splits (0 bytes: a single split / the fall-back kernel)
-    nbytes = int(lib.cn_conv_wgrad_workspace_bytes(ctypes.byref(g)))
+    ws: the caller's own fp32 workspace (at least what cn_conv_wgrad_dt_workspace_bytes reports) instead of a fresh one.
+    Which kernel runs is the library's decision (csrc/conv_dispatch.hip: plan_conv_wgrad); here only the storage types are chosen."""
+    gw, mode = out, WGRAD_ADD if accumulate else WGRAD_WRITE
+    if out is None:
+        gw, mode = zero_pool_alloc(w_shape, x.device), WGRAD_ZEROED
+        if gw is None:
+            gw, mode = torch.empty(w_shape, device=x.device, dtype=torch.float32), WGRAD_WRITE
+    # x in bf16 where the bf16 kernels take the layer, else fp32; gy as it is stored where a kernel reads that next to x (the K = 27
+    # first layers read a bf16 gy next to the fp32 image), else in x's type
+    x = _c(cast(x, torch.bfloat16 if _bf16_conv_ok(g) else torch.float32))
+    nbytes = ctypes.c_size_t(0)
+    rc = lib.cn_conv_wgrad_dt_workspace_bytes(ctypes.byref(g), _dt(x), _dt(gy), ctypes.byref(nbytes))
+    if rc == CN_EUNSUPPORTED and gy.dtype != x.dtype:
+        gy = cast(gy, x.dtype)
+        rc = lib.cn_conv_wgrad_dt_workspace_bytes(ctypes.byref(g), _dt(x), _dt(gy), ctypes.byref(nbytes))
+    check(rc, "cn_conv_wgrad_dt_workspace_bytes")
+    gy, nbytes = _c(gy), nbytes.value
+    # caller-owned workspace: the slabs of the row slices or the partial filters of the first / last layers' kernels (0 bytes: none)
     if ws is None:
         ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32) if nbytes else None
     else:
         assert ws.dtype == torch.float32 and ws.numel() * 4 >= nbytes, "conv_wgrad: workspace of %d bytes, %d needed" % (ws.numel() * 4, nbytes)
-    if nbytes and out is not None and _SINK is not None and defer:
-        # inside a backward pass (grad_sink): the row slices' slabs stay in `ws` and the pass adds the slabs of ALL its filter
-        # gradients with one grouped launch at its join (grad_sink.join) instead of one reduction launch per layer on the chain
-        parts = ctypes.c_int(0)
-        check(lib.cn_conv_wgrad_ws_slabs(ctypes.byref(g), _ptr(x), _ptr(gy), _fptr(gw), int(pre), _ptr(ws), nbytes, ctypes.byref(parts),
-                                         _stream()), "cn_conv_wgrad_ws_slabs")
-        if parts.value:
-            _SINK.slabs.append((ws, gw, parts.value, gw.numel(), int(pre)))
-        return gw
-    check(lib.cn_conv_wgrad_ws(ctypes.byref(g), _ptr(x), _ptr(gy), _fptr(gw), int(pre), _ptr(ws), nbytes, _stream()), "cn_conv_wgrad_ws")
+    # inside a backward pass (grad_sink): the row slices' slabs stay in `ws` and the pass adds the slabs of ALL its filter
+    # gradients with one grouped launch at its join (grad_sink.join) instead of one reduction launch per layer on the chain
+    parts = ctypes.c_int(0) if nbytes and out is not None and _SINK is not None and defer else None
+    check(lib.cn_conv_wgrad_dt(ctypes.byref(g), _ptr(x), _dt(x), _ptr(gy), _dt(gy), _fptr(gw), mode, _ptr(ws), nbytes,
+                               None if parts is None else ctypes.byref(parts), _stream()), "cn_conv_wgrad_dt")
+    if parts is not None and parts.value:
+        _SINK.slabs.append((ws, gw, parts.value, gw.numel(), int(mode != WGRAD_WRITE)))
     return gw
 
 

@@ -117,6 +117,31 @@ int cn_conv_wgrad_ws(const CnConvGeom* g, const float* x, const float* gy, float
  * of a backward pass instead of one reduction launch per layer.  The sum is the same bits as cn_conv_wgrad_ws's. */
 int cn_conv_wgrad_ws_slabs(const CnConvGeom* g, const float* x, const float* gy, float* gw, int accumulate, void* workspace,
                            size_t workspace_bytes, int* parts, void* stream);
+/* The ROUTED filter gradient: one call for every kernel the library has for it -- the K = 27 first layers, thin outputs, the from-RGB
+ * 1x1 shapes, the LDS-DMA kernel, the atomic row-split kernel, the bf16 kernel -- chosen from the geometry and the storage types the
+ * caller holds the operands in (CN_F32 / CN_BF16): x fp32 with gy fp32 (every geometry) or bf16 (the K = 27 layers only), or both bf16
+ * (cin % 8 == 0 and cout % 8 == 0); any other combination returns CN_EUNSUPPORTED without launching.  gw is fp32.
+ * mode: CN_WGRAD_WRITE = gw is uninitialised and is written; CN_WGRAD_ADD = the gradient is added to its contents; CN_WGRAD_ZEROED =
+ * the caller guarantees that gw holds zeros (the kernels that write need no zero pass, the ones that add simply add).
+ * workspace: cn_conv_wgrad_dt_workspace_bytes(g, x_dt, gy_dt, &bytes) bytes (0: none needed, NULL allowed); that call returns what
+ * the filter gradient itself would (CN_OK, CN_EUNSUPPORTED, CN_EINVAL).  parts = NULL: gw is complete when the call's work is; else
+ * as cn_conv_wgrad_ws_slabs: *parts >= 2 slabs are left in the workspace for the caller to add (with `mode != CN_WGRAD_WRITE` as the
+ * accumulate flag of the sum), *parts = 0: gw is complete. */
+#define CN_WGRAD_WRITE 0
+#define CN_WGRAD_ADD 1
+#define CN_WGRAD_ZEROED 2
+int cn_conv_wgrad_dt_workspace_bytes(const CnConvGeom* g, int x_dt, int gy_dt, size_t* bytes);
+int cn_conv_wgrad_dt(const CnConvGeom* g, const void* x, int x_dt, const void* gy, int gy_dt, float* gw, int mode, void* workspace,
+                     size_t workspace_bytes, int* parts, void* stream);
+/* Diagnostic: the launch a filter-gradient request WOULD get, decided exactly as the calls decide it, without a device and without
+ * enqueuing anything.  routes: bit r set = route r may be taken (-1: all of them, cn_conv_wgrad_dt; the older entry points take
+ * 4 | 16 (cn_conv_wgrad), 4 | 8 | 16 (cn_conv_wgrad_ws*), 32 (_bf16), 1 (_c3), 2 (_thin)).  out: route (0 K = 27, 1 thin, 2 from-RGB
+ * 1x1, 3 LDS-DMA kernel, 4 atomic row-split kernel, 5 bf16 kernel, 6 nothing is launched), tile (cn_conv_tune numbering, 5 = 256x64;
+ * -1: the route has none), row slices, rows per slice, profile family (cn_prof_collect_by_family slot, -1: no bracket), grid x / y / z,
+ * workspace in floats, zero pass in front of the launch when gw is to be written (0 / 1), what follows the launch (0 nothing,
+ * 1 cn_sum_parts, 2 the K = 27 kernel's own sum, 3 slabs left to the caller), stages of the LDS-DMA loop.  det: plan as in deterministic
+ * mode (1) / default mode (0), -1 = the mode in force.  Returns what the call would. */
+int cn_conv_wgrad_plan(const CnConvGeom* g, int x_dt, int gy_dt, int caller_slabs, unsigned routes, int det, long long out[12]);
 typedef struct CnSumJob {
     const float* src;     /* parts x count floats */
     float* dst;           /* count floats */

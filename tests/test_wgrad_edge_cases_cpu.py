@@ -1,6 +1,7 @@
 """What the filter-gradient edge tests (tests/test_wgrad_edges_gpu.py) rest on, checked without a GPU: the geometry table reaches
 every split class on every tile of csrc/wgrad2.hip when tile and workgroup target are forced through cn_conv_tune (so a later change
-to the plan cannot quietly empty a class), and the float64 reference on integer inputs is the integer result exactly."""
+to the plan cannot quietly empty a class), the hand replays of the slice rules agree with what cn_conv_wgrad_plan reports, and the
+float64 reference on integer inputs is the integer result exactly."""
 import pytest
 import torch
 
@@ -25,6 +26,11 @@ def test_the_table_reaches_every_split_class_on_every_tile():
         for tile in W.TILES:
             for want in W.WANTS:
                 assert plan[(tile[0], want)] == W.replayed_splits(g, tile, want), (name, tile[1], want, plan[(tile[0], want)])
+                # ... and the one the device-free report of the launch names, with the tile that was forced and whole stages per slice
+                lib.cn_conv_tune(tile[0], 0, want * W.tiles_of(g, tile))
+                rc, route, cfg, slices, rows_per, _ = W.reported_plan(g)
+                assert (rc, route, cfg, slices) == (0, 3, tile[0], W.replayed_splits(g, tile, want)), (name, tile[1], want)
+                assert rows_per % tile[4] == 0 and -(-W.rows(g) // rows_per) == slices, (name, tile[1], want, rows_per)
                 seen[tile[0]].setdefault(W.split_class(plan[(tile[0], want)]), []).append((name, want, plan[(tile[0], want)]))
     for tile in W.TILES:
         print(tile[1], {c: v for c, v in seen[tile[0]].items() if c != "1"})
@@ -86,9 +92,34 @@ def test_the_reference_on_integer_inputs_is_exact(name):
 
 
 def test_the_bf16_slice_rule_takes_the_xcd_order_where_the_tests_say():
-    """launch_bf16_wgrad's rule by hand (wgrad_edge_cases.bf16_planned_splits): the two extra bf16 shapes of the GPU test take the
+    """The bf16 kernel's slice rule by hand (wgrad_edge_cases.bf16_planned_splits): the two extra bf16 shapes of the GPU test take the
     XCD-ordered grid, one with a whole number of groups of 8 slices and one with a padded last group; no table shape does."""
     for case, want in zip(W.BF16_XCD, ((16, True), (22, True))):
         assert W.bf16_planned_splits(W.geom(case)) == want, case
     for name in W.BF16_TABLE:
         assert not W.bf16_planned_splits(W.geom(W.TABLE[name]))[1], name
+
+
+def test_the_bf16_replay_is_what_the_plan_reports():
+    """bf16_planned_splits against cn_conv_wgrad_plan for every table entry and routing shape the bf16 kernel takes and the two XCD
+    shapes, under every forced tile and target as well: the bf16 rule ignores the tuning, and so must the report."""
+    cases = list(W.TABLE.values()) + [r[1] for r in W.ROUTING] + list(W.BF16_XCD)
+    taken = 0
+    for tile in [None] + W.TILES:
+        for want in W.WANTS if tile else (0,):
+            for case in cases:
+                g = W.geom(case)
+                if tile:
+                    lib.cn_conv_tune(tile[0], 0, want * W.tiles_of(g, tile))
+                rc, route, cfg, slices, rows_per, xcd = W.reported_plan(g, bf16=True)
+                if g.cin % 8 or g.cout % 8:
+                    assert (rc, route) == (-3, 6), case
+                    continue
+                bm, bn = W.bf16_tile(g)
+                assert (rc, route) == (0, 5) and [t for t in W.TILES if t[0] == cfg][0][2:4] == (bm, bn), case
+                assert (slices, xcd) == W.bf16_planned_splits(g), (case, slices, xcd)
+                assert rows_per % 32 == 0 and -(-W.rows(g) // rows_per) == slices, (case, rows_per)
+                taken += 1
+    assert taken >= 26 * (len(W.BF16_TABLE) + 2)
+    for name in W.BF16_TABLE:
+        assert W.geom(W.TABLE[name]).cin % 8 == 0 and W.geom(W.TABLE[name]).cout % 8 == 0, name

@@ -127,7 +127,7 @@ def test_every_tile_stage_count_and_slice_plan_gives_the_integer_result(name):
 def test_the_default_plan_and_the_routing_boundaries_give_the_integer_result(name):
     """The default heuristic on the geometries next to a routing boundary of ops.conv_wgrad: the atomic kernel (Ktot < 64,
     cin % 4 != 0, cout <= 4 on wide inputs, a K = 27 layer past that route's cout limit), the thin route and the K = 27 route --
-    the kernel that takes the call is the one the profile shows -- and on the table itself, where the cost model of wg2_plan
+    the kernel that takes the call is the one the profile shows -- and on the table itself, where the cost model of cn_wgrad2_plan
     picks tile and slices (whichever tile of csrc/wgrad2.hip: the same one for the three calls)."""
     from confignet_amd import ops
     case, families = (W.TABLE[name], None) if name in W.TABLE else {r[0]: r for r in W.ROUTING}[name][1:]
@@ -204,7 +204,7 @@ def test_the_bf16_filter_gradient_gives_the_integer_result(name):
 
 @pytest.mark.parametrize("case", W.BF16_XCD, ids=["16-slices", "22-slices"])
 def test_the_bf16_filter_gradient_on_its_xcd_ordered_grid(case):
-    """Three 128x32 tiles (Ktot = 288, cout = 32) and a reduction long enough for launch_bf16_wgrad's own rule to take the
+    """Three 128x32 tiles (Ktot = 288, cout = 32) and a reduction long enough for the bf16 kernel's own slice rule to take the
     XCD-ordered 1-D grid (more than one tile, >= 16 slices).  The rule (target 2560 workgroups / 3 tiles, at most M / 512 slices,
     at least min(M / 256, 86) = one workgroup per CU, rounded down to a multiple of 8 from 16 up; rows per slice rounded up to 32):
       (16, 16, 16, 32): M = 4096 -> 16 slices of 256 rows: a grid of 2 x 8 x 3 workgroups, none of them padding;
@@ -214,6 +214,53 @@ def test_the_bf16_filter_gradient_on_its_xcd_ordered_grid(case):
     assert W.bf16_planned_splits(W.geom(case)) == ((16, True) if case[0][0] == 16 else (22, True))
     x, gy = W.integer_inputs(case, seed=17)
     _bf16_exact(case, x, gy, W.reference(x, gy, case))
+
+
+def _routed(g, x, gy, out, mode, ws):
+    """cn_conv_wgrad_dt with the workspace its own query asks for, taken from the guarded allocation `ws`"""
+    from confignet_amd import ops
+    from confignet_amd._lib import lib
+    nbytes = ctypes.c_size_t(0)
+    ops.check(lib.cn_conv_wgrad_dt_workspace_bytes(ctypes.byref(g), ops._dt(x), ops._dt(gy), ctypes.byref(nbytes)), "cn_conv_wgrad_dt_workspace_bytes")
+    assert nbytes.value <= 4 * ws.view.numel()
+    ops.check(lib.cn_conv_wgrad_dt(ctypes.byref(g), ops._ptr(x), ops._dt(x), ops._ptr(gy), ops._dt(gy), ops._fptr(out), mode,
+                                   ops._ptr(ws.view) if nbytes.value else None, nbytes.value, None, ops._stream()), "cn_conv_wgrad_dt")
+    return nbytes.value // 4
+
+
+@pytest.mark.parametrize("name", [r[0] for r in W.ROUTING] + list(W.TABLE) + ["bf16-" + n for n in W.BF16_TABLE] + ["k27-bf16-gy"])
+def test_the_routed_entry_gives_the_integer_result(name):
+    """cn_conv_wgrad_dt itself -- every route behind one call -- on the routing boundaries, the table and, with bf16 operands, the
+    table entries the bf16 kernel takes (and the K = 27 layer with a bf16 gy next to the fp32 image): written over a sentinel,
+    added to small integers, and added to a target the caller declares zero, each equal to the float64 reference bit for bit; the
+    guards around the gradient and the workspace keep their sentinel and the workspace is not written past what the query asked for."""
+    from confignet_amd import ops
+    bf16 = name.startswith("bf16-")
+    base = "k27" if name == "k27-bf16-gy" else name[5:] if bf16 else name
+    case = W.TABLE[base] if base in W.TABLE else {r[0]: r[1] for r in W.ROUTING}[base]
+    g, wshape = W.geom(case), W.filter_shape(case)
+    x64, gy64, ref64 = _exact(base)
+    x = x64.to(torch.bfloat16 if bf16 else torch.float32).cuda()
+    gy = gy64.to(torch.bfloat16 if bf16 or name == "k27-bf16-gy" else torch.float32).cuda()
+    ref = ref64.float().cuda()
+    prior = _prior(wshape, 6)
+    ref_added = (ref64 + prior.cpu().double()).float().cuda()
+    gw = Guarded(ref.numel(), UNWRITTEN)
+    out = gw.view.view(wshape)
+    nbytes = ctypes.c_size_t(0)
+    ops.check(ops.lib.cn_conv_wgrad_dt_workspace_bytes(ctypes.byref(g), ops._dt(x), ops._dt(gy), ctypes.byref(nbytes)), "cn_conv_wgrad_dt_workspace_bytes")
+    ws = Guarded(max(nbytes.value // 4, GUARD) + GUARD, float("nan"))
+    for mode, before, want in ((ops.WGRAD_WRITE, None, ref), (ops.WGRAD_ADD, prior, ref_added), (ops.WGRAD_ZEROED, torch.zeros_like(prior), ref)):
+        what = "%s mode %d" % (name, mode)
+        if before is None:
+            out.fill_(UNWRITTEN)
+        else:
+            out.copy_(before)
+        ws.view.fill_(float("nan"))
+        used = _routed(g, x, gy, out, mode, ws)
+        assert torch.equal(out, want), what + ": " + _wrong(out, want, g.cout)
+        assert gw.intact() and ws.intact(), what + ": a guard was written"
+        assert bool(torch.isnan(ws.view[used:]).all()), what + ": the workspace was written past what the query asked for"
 
 
 # ---- rounding pass ---------------------------------------------------------------------------------------------------------

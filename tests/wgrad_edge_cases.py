@@ -92,8 +92,17 @@ def planned_splits(g):
     return max(1, nbytes // (4 * ktot(g) * g.cout))
 
 
+def reported_plan(g, bf16=False):
+    """What cn_conv_wgrad_plan reports for the routed call on fp32 / bf16 operands under the tuning in force: (return code, route, tile,
+    row slices, rows per slice, XCD-ordered 1-D grid?).  Routes: csrc/common.h WgradRoute (3 = the LDS-DMA kernel, 5 = the bf16 one)."""
+    out = (ctypes.c_longlong * 12)()
+    dt = 1 if bf16 else 0
+    rc = lib.cn_conv_wgrad_plan(ctypes.byref(g), dt, dt, 0, 0xFFFFFFFF, -1, out)
+    return rc, out[0], out[1], out[2], out[3], out[6] == 1 and out[7] == 1 and out[2] > 1
+
+
 def replayed_splits(g, tile, want):
-    """The forced-target arithmetic of wg2_plan (csrc/wgrad2.hip) by hand: s = clamp((target + tiles / 2) / tiles, 1,
+    """The forced-target arithmetic of cn_wgrad2_plan (csrc/wgrad2.hip) by hand: s = clamp((target + tiles / 2) / tiles, 1,
     ceil(M / 4 KB)) slices asked for, rows per slice rounded up to KB, slices = ceil(M / rows)."""
     kb, m, tiles = tile[4], rows(g), tiles_of(g, tile)
     target = want * tiles
@@ -115,9 +124,10 @@ def bf16_tile(g):
 
 
 def bf16_planned_splits(g):
-    """launch_bf16_wgrad's slice rule (csrc/igemm_bf16.hip) by hand: (row slices, XCD-ordered 1-D grid?).  The launch itself
-    cannot be asked; this is what its rule gives, used for the number of atomic adds in the rounding bound and to show which
-    shapes take the XCD order (more than one tile and >= 16 slices; the grid is then padded to a multiple of 8 slices)."""
+    """The bf16 kernel's slice rule (csrc/conv_dispatch.hip: bf16_wgrad_slices) by hand: (row slices, XCD-ordered 1-D grid?) -- kept as
+    an independent replay of what cn_conv_wgrad_plan reports (tests/test_wgrad_edge_cases_cpu.py holds the two together).  Used for
+    the number of atomic adds in the rounding bound and to show which shapes take the XCD order (more than one tile and >= 16 slices;
+    the grid is then padded to a multiple of 8 slices)."""
     bm, bn = bf16_tile(g)
     m, tiles = rows(g), -(-ktot(g) // bm) * -(-g.cout // bn)
     per_cu = 3 if bm * bn >= 128 * 128 else 4 if bm * bn >= 128 * 96 else 5
