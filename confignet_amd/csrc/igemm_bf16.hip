@@ -431,6 +431,8 @@ int conv_bf16(const CnConvGeom& g, int flip, const bf16_t* x, const bf16_t* wb, 
     const int par = parity_ordered(g);
     // tile choice: the biggest tile that still gives >= 2 workgroups per CU (256 CUs); these kernels are memory bound,
     // occupancy hides the gather latency
+    // (tests/conv_edge_cases.py: bf16_tile replays this rule by hand to pick one test geometry per arm -- the profile family is the
+    // same for every tile, so nothing on the device tells the arms apart: change the two together)
     const long t128 = (long)cn_cdiv(M, 128) * cn_cdiv(g.cout, 128);
     const long t128x64 = (long)cn_cdiv(M, 128) * cn_cdiv(g.cout, 64);
     int cfg;
