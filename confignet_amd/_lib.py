@@ -101,7 +101,9 @@ SIGNATURES = {
     "cn_gemm": [_i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _i, _f, _p],
     "cn_nc_reduce4": [_p, _p, _i, _i, _i, _f, _i, _i, _p],
     "cn_nc_reduce": [_p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _p],
+    "cn_nc_reduce_plan": [_i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int * 8)],
     "cn_nc_lin2": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p],
+    "cn_nc_rows_plan": [ctypes.c_longlong, _i, _i, ctypes.POINTER(ctypes.c_int * 2)],
     "cn_norm_coef_fwd": [_i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _p, _i, _p],
     "cn_norm_coef_bwd": [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _p],
     "cn_dual_tail_coef_fwd": [_p] * 13 + [_i, _i, _i, _f, _i, _i, _p],

@@ -9,9 +9,6 @@
 namespace {
 
 __device__ __forceinline__ float lrelu(float v, float s) { return v > 0.f ? v : v * s; }
-__device__ __forceinline__ float4 lrelu4(float4 v, float s) {
-    return make_float4(lrelu(v.x, s), lrelu(v.y, s), lrelu(v.z, s), lrelu(v.w, s));
-}
 
 // derivative of an activation evaluated from its OUTPUT o
 __device__ __forceinline__ float act_deriv(float o, int act, float slope) {
@@ -21,303 +18,250 @@ __device__ __forceinline__ float act_deriv(float o, int act, float slope) {
     return 1.f;
 }
 
-// ---- nc_reduce: (N,S,C) -> (N,C) sums.  grid (cblk, sblk, n); block (TX c-groups, TY rows) ----
-template <int V, typename T>   // V = 4: 4-wide channel groups, V = 1: scalar channels; T: storage type of x1 / x2
-__global__ __launch_bounds__(256) void nc_reduce_kernel(const T* __restrict__ x1, const T* __restrict__ x2,
-                                                        float* __restrict__ s1, float* __restrict__ s2, int S, int C,
-                                                        int rows_per_block, int flags, float slope, int period2,
-                                                        T* __restrict__ dact_out = nullptr, int dact = 0,
-                                                        float* __restrict__ parts = nullptr, const T* __restrict__ x3 = nullptr,
-                                                        const float* __restrict__ coef = nullptr, T* __restrict__ scaled_out = nullptr,
-                                                        int dact_on = 0) {
-    // dact_on: fused activation backward -- a = x1 * act'(x2) (x2 = the activation's OUTPUT); a is written to dact_out (if given),
-    // coef[c] * a to scaled_out (if given: the input gradient of an inference-mode BatchNorm), s1 = sum a, s2 = sum a * (x3 if
-    // given, else f2(x2)): the whole backward of conv -> BN(inference) -> ReLU in one pass (cn_bn_act_bwd)
+// ---- (N,S,C) -> (N,C) reductions: ONE row walk (nc_reduce_rows), three operand sets (NcSumDot, NcStats4, NcHxt) ----
+// grid (cblk, sblk, n); block (TX channel groups, TY rows): plan_nc_reduce below.  An operand set supplies begin() (the addresses
+// of one (sample, channel group)), load<U>() (U rows of every array it reads: all rows of one array, then the next array) and add()
+// (one loaded row into acc[Q][V]).
+
+template <int V> struct RowV { float v[V]; };      // the V channels of a group in one row (V = 4: 4-wide groups, V = 1: scalar channels)
+
+template <int V, typename T>
+__device__ __forceinline__ RowV<V> ld_row(const T* p) {
+    RowV<V> r;
+    if constexpr (V == 4) {
+        const float4 t = ld4<T>(p);
+        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
+    } else {
+        r.v[0] = ldf<T>(p);
+    }
+    return r;
+}
+template <int V, typename T>
+__device__ __forceinline__ void st_row(T* p, const RowV<V>& r) {
+    if constexpr (V == 4) st4<T>(p, make_float4(r.v[0], r.v[1], r.v[2], r.v[3]));
+    else stf<T>(p, r.v[0]);
+}
+
+template <int Q, int V, typename Op>
+__device__ __forceinline__ void nc_reduce_rows(Op op, float* const (&out)[Q], int S, int C, int rows_per_block, float* __restrict__ parts) {
     const int CG = C / V;                          // channel groups
     const int tx = threadIdx.x, ty = threadIdx.y, TX = blockDim.x, TY = blockDim.y;
     const int cg = blockIdx.x * TX + tx;
     const int n = blockIdx.z;
     const int sbeg = blockIdx.y * rows_per_block, send = min(S, sbeg + rows_per_block);
-    float a1[V], a2[V];
+    float acc[Q][V];
 #pragma unroll
-    for (int e = 0; e < V; ++e) a1[e] = a2[e] = 0.f;
+    for (int q = 0; q < Q; ++q)
+#pragma unroll
+        for (int e = 0; e < V; ++e) acc[q][e] = 0.f;
     if (cg < CG) {
-        const long base = (long)n * S * C + (long)cg * V;
-        const long base2 = (long)(period2 ? n % period2 : n) * S * C + (long)cg * V;     // x2 may hold fewer samples (tiled)
+        op.begin(n, cg, S, C);
         int s = sbeg + ty;
         if (V == 4) {
             // four rows in flight per thread: with ~2 workgroups per CU (the same-address atomics of the epilogue bound the workgroup
             // count) one dependent 16-byte load per array kept 16 KB per CU on the wire -- 3.4 TB/s on the largest tensors, 5.6 now
             for (; s + 3 * TY < send; s += 4 * TY) {
-                float4 va[4], vb[4], vc[4];
+                typename Op::Row r[4];
+                op.load(r, s, TY, C);
 #pragma unroll
-                for (int u = 0; u < 4; ++u) va[u] = ld4<T>(x1 + base + (long)(s + u * TY) * C);
-                if (x2) {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) vb[u] = ld4<T>(x2 + base2 + (long)(s + u * TY) * C);
-                }
-                if (dact_on && x3) {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) vc[u] = ld4<T>(x3 + base + (long)(s + u * TY) * C);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    float4 a = va[u], b = vb[u];
-                    if (flags & 1) a = lrelu4(a, slope);
-                    if (dact_on) {                 // (the derivative from x2 itself, before f2: f2 belongs to the second sum only)
-                        a.x *= act_deriv(b.x, dact, slope); a.y *= act_deriv(b.y, dact, slope);
-                        a.z *= act_deriv(b.z, dact, slope); a.w *= act_deriv(b.w, dact, slope);
-                    }
-                    if (x2) { if (flags & 2) b = lrelu4(b, slope); }
-                    if (dact_on) {
-                        if (dact_out) st4<T>(dact_out + base + (long)(s + u * TY) * C, a);
-                        if (scaled_out) {
-                            const float4 k4 = *reinterpret_cast<const float4*>(coef + (long)cg * V);
-                            st4<T>(scaled_out + base + (long)(s + u * TY) * C, make_float4(a.x * k4.x, a.y * k4.y, a.z * k4.z, a.w * k4.w));
-                        }
-                        if (x3) b = vc[u];
-                    }
-                    if (!x2) b = a;
-                    a1[0] += a.x; a1[1 % V] += a.y; a1[2 % V] += a.z; a1[3 % V] += a.w;
-                    a2[0] += a.x * b.x; a2[1 % V] += a.y * b.y; a2[2 % V] += a.z * b.z; a2[3 % V] += a.w * b.w;
-                }
+                for (int u = 0; u < 4; ++u) op.add(acc, r[u], (long)(s + u * TY) * C);
             }
         }
         for (; s < send; s += TY) {
-            float a[V], b[V];
-            if (V == 4) {
-                float4 va = ld4<T>(x1 + base + (long)s * C);
-                if (flags & 1) va = lrelu4(va, slope);
-                a[0] = va.x; a[1 % V] = va.y; a[2 % V] = va.z; a[3 % V] = va.w;
-                if (x2) {
-                    float4 vb = ld4<T>(x2 + base2 + (long)s * C);
-                    if (dact_on) {
-                        a[0] *= act_deriv(vb.x, dact, slope); a[1 % V] *= act_deriv(vb.y, dact, slope);
-                        a[2 % V] *= act_deriv(vb.z, dact, slope); a[3 % V] *= act_deriv(vb.w, dact, slope);
-                    }
-                    if (flags & 2) vb = lrelu4(vb, slope);
-                    b[0] = vb.x; b[1 % V] = vb.y; b[2 % V] = vb.z; b[3 % V] = vb.w;
-                }
-                if (dact_on) {
-                    if (dact_out) st4<T>(dact_out + base + (long)s * C, make_float4(a[0], a[1 % V], a[2 % V], a[3 % V]));
-                    if (scaled_out) {
-                        const float4 k4 = *reinterpret_cast<const float4*>(coef + (long)cg * V);
-                        st4<T>(scaled_out + base + (long)s * C, make_float4(a[0] * k4.x, a[1 % V] * k4.y, a[2 % V] * k4.z, a[3 % V] * k4.w));
-                    }
-                    if (x3) {
-                        const float4 vc = ld4<T>(x3 + base + (long)s * C);
-                        b[0] = vc.x; b[1 % V] = vc.y; b[2 % V] = vc.z; b[3 % V] = vc.w;
-                    }
-                }
-            } else {
-                a[0] = ldf<T>(x1 + base + (long)s * C);
-                if (flags & 1) a[0] = lrelu(a[0], slope);
-                if (x2) {
-                    b[0] = ldf<T>(x2 + base2 + (long)s * C);
-                    if (dact_on) a[0] *= act_deriv(b[0], dact, slope);
-                    if (flags & 2) b[0] = lrelu(b[0], slope);
-                }
-                if (dact_on) {
-                    if (dact_out) stf<T>(dact_out + base + (long)s * C, a[0]);
-                    if (scaled_out) stf<T>(scaled_out + base + (long)s * C, a[0] * coef[cg]);
-                    if (x3) b[0] = ldf<T>(x3 + base + (long)s * C);
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < V; ++e) {
-                a1[e] += a[e];
-                a2[e] += a[e] * (x2 ? b[e] : a[e]);
-            }
+            typename Op::Row r[1];
+            op.load(r, s, TY, C);
+            op.add(acc, r[0], (long)s * C);
         }
     }
-    __shared__ float red[2][256 * V];
+    __shared__ float red[Q][256 * V];
 #pragma unroll
-    for (int e = 0; e < V; ++e) {
-        red[0][(ty * TX + tx) * V + e] = a1[e];
-        red[1][(ty * TX + tx) * V + e] = a2[e];
-    }
+    for (int q = 0; q < Q; ++q)
+#pragma unroll
+        for (int e = 0; e < V; ++e) red[q][(ty * TX + tx) * V + e] = acc[q][e];
     __syncthreads();
     if (ty == 0 && cg < CG) {
+        const bool one_block = rows_per_block >= S;        // gridDim.y == 1, from arguments the walk already holds (no late scalar load)
 #pragma unroll
         for (int e = 0; e < V; ++e) {
-            float t1 = 0.f, t2 = 0.f;
+            float t[Q];
+#pragma unroll
+            for (int q = 0; q < Q; ++q) t[q] = 0.f;
             for (int y = 0; y < TY; ++y) {
-                t1 += red[0][(y * TX + tx) * V + e];
-                t2 += red[1][(y * TX + tx) * V + e];
+#pragma unroll
+                for (int q = 0; q < Q; ++q) t[q] += red[q][(y * TX + tx) * V + e];
             }
             const long o = (long)n * C + (long)cg * V + e;
             if (parts) {                           // deterministic mode: per-row-block partials, added in block order afterwards
                 const long nc = (long)gridDim.z * C;
-                if (s1) parts[(long)blockIdx.y * nc + o] = t1;
-                if (s2) parts[((long)gridDim.y + blockIdx.y) * nc + o] = t2;
-            } else if (gridDim.y == 1) {           // the only workgroup of this (n, channel block): plain stores
-                if (s1) s1[o] = t1;
-                if (s2) s2[o] = t2;
+#pragma unroll
+                for (int q = 0; q < Q; ++q)
+                    if (out[q]) parts[((long)q * gridDim.y + blockIdx.y) * nc + o] = t[q];
+            } else if (one_block) {                // the only workgroup of this (n, channel block): plain stores
+#pragma unroll
+                for (int q = 0; q < Q; ++q)
+                    if (out[q]) out[q][o] = t[q];
             } else {
-                if (s1) unsafeAtomicAdd(&s1[o], t1);
-                if (s2) unsafeAtomicAdd(&s2[o], t2);
+#pragma unroll
+                for (int q = 0; q < Q; ++q)
+                    if (out[q]) unsafeAtomicAdd(&out[q][o], t[q]);
             }
         }
     }
 }
 
-// ---- nc_reduce4: the four statistics of a DiscrBlock's tail in ONE pass over its pre-activation tensor ----
-// out[0] = sum x, out[1] = sum x^2 (the layer style, confignet_utils.py:147-159), out[2] = sum l, out[3] = sum l^2 with
-// l = leaky_relu(x) (the instance normalisation behind the activation, building_blocks.py:100-106); out is (4, N, C), zeroed by
-// the caller unless gridDim.y == 1.  Same grid as nc_reduce_kernel<4>.
+// out[0] = sum f1(x1), out[1] = sum f1(x1) f2(x2 or x1).  dact_on: fused activation backward -- a = x1 * act'(x2) (x2 = the
+// activation's OUTPUT; the derivative from x2 itself, before f2: f2 belongs to the second sum only); a is written to dact_out (if
+// given), coef[c] * a to scaled_out (if given: the input gradient of an inference-mode BatchNorm), out[0] = sum a, out[1] = sum a *
+// (x3 if given, else f2(x2)): the whole backward of conv -> BN(inference) -> ReLU in one pass (cn_bn_act_bwd)
+template <int V, typename T>
+struct NcSumDot {
+    const T* x1; const T* x2; const T* x3; T* dact_out; T* scaled_out; const float* coef;
+    int flags, period2, dact, dact_on;
+    float slope;
+    long base, base2;
+    int cg;
+    struct Row { RowV<V> a, b, c; };
+    __device__ __forceinline__ void begin(int n, int cg_, int S, int C) {
+        cg = cg_;
+        base = (long)n * S * C + (long)cg * V;
+        base2 = (long)(period2 ? n % period2 : n) * S * C + (long)cg * V;     // x2 may hold fewer samples (tiled)
+    }
+    template <int U>
+    __device__ __forceinline__ void load(Row (&r)[U], int s, int TY, int C) const {
+#pragma unroll
+        for (int u = 0; u < U; ++u) r[u].a = ld_row<V, T>(x1 + base + (long)(s + u * TY) * C);
+        if (x2) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) r[u].b = ld_row<V, T>(x2 + base2 + (long)(s + u * TY) * C);
+        }
+        if (dact_on && x3) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) r[u].c = ld_row<V, T>(x3 + base + (long)(s + u * TY) * C);
+        }
+    }
+    __device__ __forceinline__ void add(float (&acc)[2][V], const Row& r, long off) const {
+        RowV<V> a = r.a, b = r.b;
+        if (flags & 1) {                           // (each option decided once per row, not per channel)
+#pragma unroll
+            for (int e = 0; e < V; ++e) a.v[e] = lrelu(a.v[e], slope);
+        }
+        if (dact_on) {
+#pragma unroll
+            for (int e = 0; e < V; ++e) a.v[e] *= act_deriv(b.v[e], dact, slope);
+        }
+        if (x2 && (flags & 2)) {
+#pragma unroll
+            for (int e = 0; e < V; ++e) b.v[e] = lrelu(b.v[e], slope);
+        }
+        if (dact_on) {
+            if (dact_out) st_row<V, T>(dact_out + base + off, a);
+            if (scaled_out) {
+                RowV<V> k = ld_row<V, float>(coef + (long)cg * V);
+#pragma unroll
+                for (int e = 0; e < V; ++e) k.v[e] = a.v[e] * k.v[e];
+                st_row<V, T>(scaled_out + base + off, k);
+            }
+            if (x3) b = r.c;
+        }
+        if (!x2) b = a;
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            acc[0][e] += a.v[e];
+            acc[1][e] += a.v[e] * b.v[e];
+        }
+    }
+};
+
+// The four statistics of a DiscrBlock's tail in ONE pass over its pre-activation tensor: out[0] = sum x, out[1] = sum x^2 (the layer
+// style, confignet_utils.py:147-159), out[2] = sum l, out[3] = sum l^2 with l = leaky_relu(x) (the instance normalisation behind the
+// activation, building_blocks.py:100-106)
 template <typename T>
+struct NcStats4 {
+    const T* x;
+    float slope;
+    long base;
+    struct Row { RowV<4> x; };
+    __device__ __forceinline__ void begin(int n, int cg, int S, int C) { base = (long)n * S * C + (long)cg * 4; }
+    template <int U>
+    __device__ __forceinline__ void load(Row (&r)[U], int s, int TY, int C) const {
+#pragma unroll
+        for (int u = 0; u < U; ++u) r[u].x = ld_row<4, T>(x + base + (long)(s + u * TY) * C);
+    }
+    __device__ __forceinline__ void add(float (&acc)[4][4], const Row& r, long) const {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float a = r.x.v[e], b = lrelu(a, slope);
+            acc[0][e] += a;
+            acc[1][e] += a * a;
+            acc[2][e] += b;
+            acc[3][e] += b * b;
+        }
+    }
+};
+
+// The three reductions of the R1 tangent tail's backward pass in ONE pass over its cotangent: out[0] = sum h, out[1] = sum h lrelu(x),
+// out[2] = sum h ta per (n, c); h and ta hold gridDim.z samples, x `period` samples (read through the sample period).
+// ta_is_tx: the third operand is the tangent INPUT tx; ta = lrelu'(x) tx is formed here (it is never stored)
+template <typename T>
+struct NcHxt {
+    const T* h; const T* x; const T* ta;
+    float slope;
+    int period, ta_is_tx;
+    long base, base2;
+    struct Row { RowV<4> h, x, t; };
+    __device__ __forceinline__ void begin(int n, int cg, int S, int C) {
+        base = (long)n * S * C + (long)cg * 4;
+        base2 = (long)(n % period) * S * C + (long)cg * 4;
+    }
+    template <int U>
+    __device__ __forceinline__ void load(Row (&r)[U], int s, int TY, int C) const {
+#pragma unroll
+        for (int u = 0; u < U; ++u) r[u].h = ld_row<4, T>(h + base + (long)(s + u * TY) * C);
+#pragma unroll
+        for (int u = 0; u < U; ++u) r[u].x = ld_row<4, T>(x + base2 + (long)(s + u * TY) * C);
+#pragma unroll
+        for (int u = 0; u < U; ++u) r[u].t = ld_row<4, T>(ta + base + (long)(s + u * TY) * C);
+    }
+    __device__ __forceinline__ void add(float (&acc)[3][4], const Row& r, long) const {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float a = r.h.v[e], xr = r.x.v[e], b = lrelu(xr, slope);
+            float t = r.t.v[e];
+            if (ta_is_tx) t *= xr > 0.f ? 1.f : slope;
+            acc[0][e] += a;
+            acc[1][e] += a * b;
+            acc[2][e] += a * t;
+        }
+    }
+};
+
+template <int V, typename T>   // T: storage type of x1 / x2 / x3 and of the two maps
+__global__ __launch_bounds__(256) void nc_reduce_kernel(const T* __restrict__ x1, const T* __restrict__ x2,
+                                                        float* __restrict__ s1, float* __restrict__ s2, int S, int C,
+                                                        int rows_per_block, int flags, float slope, int period2,
+                                                        T* __restrict__ dact_out, int dact, float* __restrict__ parts,
+                                                        const T* __restrict__ x3, const float* __restrict__ coef,
+                                                        T* __restrict__ scaled_out, int dact_on) {
+    float* const out[2] = {s1, s2};
+    nc_reduce_rows<2, V>(NcSumDot<V, T>{x1, x2, x3, dact_out, scaled_out, coef, flags, period2, dact, dact_on, slope}, out, S, C,
+                         rows_per_block, parts);
+}
+
+template <typename T>          // out is (4, N, C)
 __global__ __launch_bounds__(256) void nc_reduce4_kernel(const T* __restrict__ x, float* __restrict__ out, int S, int C,
                                                          int rows_per_block, float slope, float* __restrict__ parts) {
-    const int CG = C / 4;
-    const int tx = threadIdx.x, ty = threadIdx.y, TX = blockDim.x, TY = blockDim.y;
-    const int cg = blockIdx.x * TX + tx;
-    const int n = blockIdx.z;
-    const int sbeg = blockIdx.y * rows_per_block, send = min(S, sbeg + rows_per_block);
-    float acc[4][4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[q][e] = 0.f;
-    if (cg < CG) {
-        const long base = (long)n * S * C + (long)cg * 4;
-        int s = sbeg + ty;
-        for (; s + 3 * TY < send; s += 4 * TY) {       // four rows in flight (see nc_reduce_kernel)
-            float4 vv[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) vv[u] = ld4<T>(x + base + (long)(s + u * TY) * C);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float4 l = lrelu4(vv[u], slope);
-                const float a[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w}, b[4] = {l.x, l.y, l.z, l.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    acc[0][e] += a[e];
-                    acc[1][e] += a[e] * a[e];
-                    acc[2][e] += b[e];
-                    acc[3][e] += b[e] * b[e];
-                }
-            }
-        }
-        for (; s < send; s += TY) {
-            const float4 v = ld4<T>(x + base + (long)s * C);
-            const float4 l = lrelu4(v, slope);
-            const float a[4] = {v.x, v.y, v.z, v.w}, b[4] = {l.x, l.y, l.z, l.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                acc[0][e] += a[e];
-                acc[1][e] += a[e] * a[e];
-                acc[2][e] += b[e];
-                acc[3][e] += b[e] * b[e];
-            }
-        }
-    }
-    __shared__ float red[4][256 * 4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) red[q][(ty * TX + tx) * 4 + e] = acc[q][e];
-    __syncthreads();
-    if (ty == 0 && cg < CG) {
-        const long nc = (long)gridDim.z * C;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float t = 0.f;
-                for (int y = 0; y < TY; ++y) t += red[q][(y * TX + tx) * 4 + e];
-                const long o = (long)n * C + (long)cg * 4 + e;
-                if (parts) parts[((long)q * gridDim.y + blockIdx.y) * nc + o] = t;     // deterministic mode: ordered second pass
-                else if (gridDim.y == 1) out[q * nc + o] = t;
-                else unsafeAtomicAdd(&out[q * nc + o], t);
-            }
-    }
+    const long nc = (long)gridDim.z * C;
+    float* const o[4] = {out, out + nc, out + 2 * nc, out + 3 * nc};
+    nc_reduce_rows<4, 4>(NcStats4<T>{x, slope}, o, S, C, rows_per_block, parts);
 }
 
-// ---- nc_reduce_hxt: the three reductions of the R1 tangent tail's backward pass in ONE pass over its cotangent (round 6) ----
-// out[0] = sum h, out[1] = sum h lrelu(x), out[2] = sum h ta per (n, c); h and ta hold gridDim.z samples, x `period` samples
-// (read through the sample period); out is (3, N, C), zeroed by the caller unless gridDim.y == 1.  Grid as nc_reduce_kernel<4>.
-template <typename T>
+template <typename T>          // out is (3, N, C)
 __global__ __launch_bounds__(256) void nc_reduce_hxt_kernel(const T* __restrict__ h, const T* __restrict__ x, const T* __restrict__ ta,
                                                             float* __restrict__ out, int S, int C, int rows_per_block, float slope,
                                                             int period, float* __restrict__ parts, int ta_is_tx) {
-    // ta_is_tx: the third operand is the tangent INPUT tx; ta = lrelu'(x) tx is formed here (it is never stored)
-    const int CG = C / 4;
-    const int tx = threadIdx.x, ty = threadIdx.y, TX = blockDim.x, TY = blockDim.y;
-    const int cg = blockIdx.x * TX + tx;
-    const int n = blockIdx.z;
-    const int sbeg = blockIdx.y * rows_per_block, send = min(S, sbeg + rows_per_block);
-    float acc[3][4];
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[q][e] = 0.f;
-    if (cg < CG) {
-        const long base = (long)n * S * C + (long)cg * 4;
-        const long base2 = (long)(n % period) * S * C + (long)cg * 4;
-        int s = sbeg + ty;
-        for (; s + 3 * TY < send; s += 4 * TY) {       // four rows in flight (see nc_reduce_kernel)
-            float4 vh[4], vx[4], vt[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) vh[u] = ld4<T>(h + base + (long)(s + u * TY) * C);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) vx[u] = ld4<T>(x + base2 + (long)(s + u * TY) * C);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) vt[u] = ld4<T>(ta + base + (long)(s + u * TY) * C);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float4 l = lrelu4(vx[u], slope);
-                const float a[4] = {vh[u].x, vh[u].y, vh[u].z, vh[u].w}, b[4] = {l.x, l.y, l.z, l.w},
-                            xr[4] = {vx[u].x, vx[u].y, vx[u].z, vx[u].w};
-                float t[4] = {vt[u].x, vt[u].y, vt[u].z, vt[u].w};
-                if (ta_is_tx) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) t[e] *= xr[e] > 0.f ? 1.f : slope;
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    acc[0][e] += a[e];
-                    acc[1][e] += a[e] * b[e];
-                    acc[2][e] += a[e] * t[e];
-                }
-            }
-        }
-        for (; s < send; s += TY) {
-            const float4 vh = ld4<T>(h + base + (long)s * C), vxr = ld4<T>(x + base2 + (long)s * C), l = lrelu4(vxr, slope),
-                         vt = ld4<T>(ta + base + (long)s * C);
-            const float a[4] = {vh.x, vh.y, vh.z, vh.w}, b[4] = {l.x, l.y, l.z, l.w}, xr[4] = {vxr.x, vxr.y, vxr.z, vxr.w};
-            float t[4] = {vt.x, vt.y, vt.z, vt.w};
-            if (ta_is_tx) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) t[e] *= xr[e] > 0.f ? 1.f : slope;
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                acc[0][e] += a[e];
-                acc[1][e] += a[e] * b[e];
-                acc[2][e] += a[e] * t[e];
-            }
-        }
-    }
-    __shared__ float red[3][256 * 4];
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) red[q][(ty * TX + tx) * 4 + e] = acc[q][e];
-    __syncthreads();
-    if (ty == 0 && cg < CG) {
-        const long nc = (long)gridDim.z * C;
-#pragma unroll
-        for (int q = 0; q < 3; ++q)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float t = 0.f;
-                for (int y = 0; y < TY; ++y) t += red[q][(y * TX + tx) * 4 + e];
-                const long o = (long)n * C + (long)cg * 4 + e;
-                if (parts) parts[((long)q * gridDim.y + blockIdx.y) * nc + o] = t;     // deterministic mode: ordered second pass
-                else if (gridDim.y == 1) out[q * nc + o] = t;
-                else unsafeAtomicAdd(&out[q * nc + o], t);
-            }
-    }
+    const long nc = (long)gridDim.z * C;
+    float* const o[3] = {out, out + nc, out + 2 * nc};
+    nc_reduce_rows<3, 4>(NcHxt<T>{h, x, ta, slope, period, ta_is_tx}, o, S, C, rows_per_block, parts);
 }
 
 // ---- nc_lin2: y = A1*f1(x1) + A2*f2(x2) + B ----
@@ -1050,65 +994,95 @@ inline int ew_blocks(size_t n) {
 
 }  // namespace
 
+// ---- the launch of an (n, s, c) -> (n, c) reduction: decided here, performed by nc_reduce_run ("Statistics dispatch") ----
+struct NcReducePlan {
+    int V;                    // channels per thread: 4 (c % 4 == 0) or 1
+    int TX, TY;               // block: TX channel groups x TY rows, 256 threads
+    int cblk, sblk;           // grid: channel blocks x row blocks (x n samples)
+    int rows_per_block;
+    int zero_first;           // the kernel adds with atomics: clear the outputs before it
+    long parts_floats;        // deterministic mode: the per-row-block partials, [nsums][sblk][n][c]
+};
+
+// Pure.  ~512 workgroups in total (sweep: fewer, longer workgroups = shorter same-address atomic tails), at most 256 row blocks
+// (same-address atomics serialise, ~100 ns each: 2048 per address cost 200 us), at least 4*TY rows each (the four rows in flight).
+static NcReducePlan plan_nc_reduce(int n, int s, int c, int nsums, bool prezeroed, bool det) {
+    NcReducePlan p;
+    p.V = (c % 4 == 0) ? 4 : 1;
+    const int CG = c / p.V;
+    p.TX = 1;
+    while (p.TX < CG && p.TX < 64) p.TX <<= 1;
+    p.TY = 256 / p.TX;
+    p.cblk = cn_cdiv(CG, p.TX);
+    long want = 512 / ((long)p.cblk * n);
+    if (want < 1) want = 1;
+    if (want > 256) want = 256;
+    long rpb = (s + want - 1) / want;
+    if (rpb < 4 * p.TY) rpb = 4 * p.TY;
+    p.rows_per_block = (int)rpb;
+    p.sblk = cn_cdiv(s, rpb);
+    p.zero_first = p.sblk > 1 && !det && !prezeroed;      // (one row block: plain stores; deterministic: cn_sum_parts overwrites)
+    p.parts_floats = (det && p.sblk > 1) ? (long)nsums * p.sblk * n * c : 0;      // <= nsums * 512 * 256, far below CN_DET_WS_FLOATS
+    return p;
+}
+
+extern "C" int cn_nc_reduce_plan(int n, int s, int c, int nsums, int prezeroed, int det, int out[8]) {
+    CN_CHECK_ARG(n > 0 && s > 0 && c > 0 && nsums >= 1 && nsums <= 4 && out, "nc_reduce_plan: bad args");
+    const NcReducePlan p = plan_nc_reduce(n, s, c, nsums, prezeroed != 0, det != 0);
+    const int v[8] = {p.V, p.TX, p.TY, p.cblk, p.sblk, p.rows_per_block, p.zero_first, (int)p.parts_floats};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return CN_OK;
+}
+
+// The one launcher: clear (adjacent outputs by one launch), deterministic workspace, launch(plan, grid, block, parts), ordered sums.
+// out[q] may be NULL (that sum is not wanted).
+template <int Q, typename Launch>
+static int nc_reduce_run(float* const (&out)[Q], int n, int s, int c, bool prezeroed, hipStream_t st, Launch launch) {
+    const NcReducePlan p = plan_nc_reduce(n, s, c, Q, prezeroed, cn_det() != 0);
+    const size_t nc = (size_t)n * c;
+    if (p.zero_first) {
+        for (int q = 0, e; q < Q; q = e) {
+            e = q + 1;
+            if (!out[q]) continue;
+            while (e < Q && out[e] == out[q] + (e - q) * nc) ++e;
+            if (int ez__ = cn_zero_async(out[q], sizeof(float) * nc * (e - q), st)) return ez__;
+        }
+    }
+    float* parts = nullptr;
+    if (p.parts_floats) {
+        parts = cn_det_ws(st, (size_t)p.parts_floats);
+        if (!parts) return CN_EINVAL;
+    }
+    launch(p, dim3(p.cblk, p.sblk, n), dim3(p.TX, p.TY), parts);
+    CN_LAUNCH_CHECK();
+    if (parts) {
+        for (int q = 0; q < Q; ++q)
+            if (out[q]) {
+                if (int e = cn_sum_parts(parts + (size_t)q * p.sblk * nc, out[q], p.sblk, (long)nc, 0, 1.f, st)) return e;
+            }
+    }
+    return CN_OK;
+}
+
 static int nc_reduce_launch(const void* x1, const void* x2, float* s1, float* s2, int n, int s, int c, int flags,
                             float slope, int dt, void* stream, void* dact_out, int dact, const void* x3 = nullptr,
                             const float* coef = nullptr, void* scaled_out = nullptr, int dact_on = -1) {
     if (dact_on < 0) dact_on = dact_out != nullptr;
     CN_CHECK_ARG(x1 && (s1 || s2) && n > 0 && s > 0 && c > 0 && (dt == CN_F32 || dt == CN_BF16), "nc_reduce: bad args");
-    hipStream_t st = (hipStream_t)stream;
-    if (flags & 16) {
-        // outputs were cleared by the caller (per-step zero pool: one clearing launch per step, not per call)
-    } else if (s1 && s2 == s1 + (size_t)n * c) {
-        if (int ez__ = cn_zero_async(s1, sizeof(float) * 2 * (size_t)n * c, st)) return ez__;
-    } else {
-        if (s1) {
-            if (int ez__ = cn_zero_async(s1, sizeof(float) * (size_t)n * c, st)) return ez__;
-        }
-        if (s2) {
-            if (int ez__ = cn_zero_async(s2, sizeof(float) * (size_t)n * c, st)) return ez__;
-        }
-    }
-    const int V = (c % 4 == 0) ? 4 : 1;
-    const int CG = c / V;
-    int TX = 1;
-    while (TX < CG && TX < 64) TX <<= 1;
-    const int TY = 256 / TX;
-    const int cblk = cn_cdiv(CG, TX);
-    // ~512 workgroups in total, at least 4*TY rows each
-    constexpr long red_blocks = 512;   // sweep: fewer, longer workgroups = shorter same-address atomic tails
-    long want = red_blocks / ((long)cblk * n);
-    if (cn_det()) {                 // deterministic mode: as many row blocks as the per-stream workspace holds partials for
-        const long cap = (long)(CN_DET_WS_FLOATS / (2 * (size_t)n * c));
-        if (want > cap) want = cap;
-    }
-    if (want < 1) want = 1;
-    if (want > 256) want = 256;     // same-address atomics serialise (~100 ns each): 2048 per address cost 200 us
-    long rpb = (s + want - 1) / want;
-    if (rpb < 4 * TY) rpb = 4 * TY;
-    const int sblk = cn_cdiv(s, rpb);
-    dim3 grid(cblk, sblk, n), block(TX, TY);
     const int period2 = flags >> 8;                 // bits 8..: x2 holds `period2` samples, used for sample n as n % period2
     CN_CHECK_ARG(period2 == 0 || (x2 && n % period2 == 0), "nc_reduce: bad x2 period %d for n = %d", period2, n);
-    float* parts = nullptr;
-    if (cn_det() && sblk > 1) {
-        parts = cn_det_ws(st, 2 * (size_t)sblk * n * c);
-        if (!parts) return CN_EINVAL;
-    }
-    CN_DISPATCH_DT(dt, {
-        const T* p1 = (const T*)x1; const T* p2 = (const T*)x2;
-        if (V == 4) hipLaunchKernelGGL((nc_reduce_kernel<4, T>), grid, block, 0, st, p1, p2, s1, s2, s, c, (int)rpb, flags & 255, slope, period2, (T*)dact_out, dact, parts, (const T*)x3, coef, (T*)scaled_out, dact_on);
-        else hipLaunchKernelGGL((nc_reduce_kernel<1, T>), grid, block, 0, st, p1, p2, s1, s2, s, c, (int)rpb, flags & 255, slope, period2, (T*)dact_out, dact, parts, (const T*)x3, coef, (T*)scaled_out, dact_on);
+    hipStream_t st = (hipStream_t)stream;
+    float* const out[2] = {s1, s2};
+    // flags bit 4: the outputs were cleared by the caller (per-step zero pool: one clearing launch per step, not per call)
+    return nc_reduce_run(out, n, s, c, (flags & 16) != 0, st, [&](const NcReducePlan& p, dim3 grid, dim3 block, float* parts) {
+        CN_DISPATCH_DT(dt, {
+            const T* p1 = (const T*)x1; const T* p2 = (const T*)x2;
+            if (p.V == 4) hipLaunchKernelGGL((nc_reduce_kernel<4, T>), grid, block, 0, st, p1, p2, s1, s2, s, c, p.rows_per_block, flags & 255, slope, period2, (T*)dact_out, dact, parts, (const T*)x3, coef, (T*)scaled_out, dact_on);
+            else hipLaunchKernelGGL((nc_reduce_kernel<1, T>), grid, block, 0, st, p1, p2, s1, s2, s, c, p.rows_per_block, flags & 255, slope, period2, (T*)dact_out, dact, parts, (const T*)x3, coef, (T*)scaled_out, dact_on);
+        });
     });
-    CN_LAUNCH_CHECK();
-    if (parts) {
-        if (s1) { if (int e = cn_sum_parts(parts, s1, sblk, (long)n * c, 0, 1.f, st)) return e; }
-        if (s2) { if (int e = cn_sum_parts(parts + (size_t)sblk * n * c, s2, sblk, (long)n * c, 0, 1.f, st)) return e; }
-    }
-    return CN_OK;
 }
 
-// out (4, n, c) = sum x, sum x^2, sum lrelu(x), sum lrelu(x)^2 over s: the style statistics and the instance-norm statistics of a
-// DiscrBlock's pre-activation tensor in one pass (c % 4 == 0).  flags bit4: `out` is already zero.
 // (sum h, sum h lrelu(x), sum h ta) per (n, c) in one pass: out (3, n, c); x holds `period` samples (n % period == 0); flags & 16:
 // out is already zero; flags & 32: `ta` is the tangent input tx and ta = lrelu'(x) tx is formed in the pass.  The backward reductions of the DiscrBlock tail's tangent (losses.py:75-82 through building_blocks.py:100-106).
 extern "C" int cn_nc_reduce_hxt(const void* h, const void* x, const void* ta, float* out, int n, int s, int c, float slope, int period,
@@ -1116,72 +1090,24 @@ extern "C" int cn_nc_reduce_hxt(const void* h, const void* x, const void* ta, fl
     CN_CHECK_ARG(h && x && ta && out && n > 0 && s > 0 && c > 0 && c % 4 == 0 && period > 0 && n % period == 0 && (dt == CN_F32 || dt == CN_BF16),
                  "nc_reduce_hxt: bad args");
     hipStream_t st = (hipStream_t)stream;
-    const int CG = c / 4;
-    int TX = 1;
-    while (TX < CG && TX < 64) TX <<= 1;
-    const int TY = 256 / TX;
-    const int cblk = cn_cdiv(CG, TX);
-    long want = 512 / ((long)cblk * n);
-    if (cn_det()) {
-        const long cap = (long)(CN_DET_WS_FLOATS / (3 * (size_t)n * c));
-        if (want > cap) want = cap;
-    }
-    if (want < 1) want = 1;
-    if (want > 256) want = 256;
-    long rpb = (s + want - 1) / want;
-    if (rpb < 4 * TY) rpb = 4 * TY;
-    const int sblk = cn_cdiv(s, rpb);
-    float* parts = nullptr;
-    if (cn_det() && sblk > 1) {
-        parts = cn_det_ws(st, 3 * (size_t)sblk * n * c);
-        if (!parts) return CN_EINVAL;
-    } else if (sblk > 1 && !(flags & 16)) {
-        if (int ez__ = cn_zero_async(out, sizeof(float) * 3 * (size_t)n * c, st)) return ez__;
-    }
-    dim3 grid(cblk, sblk, n), block(TX, TY);
-    CN_DISPATCH_DT(dt, hipLaunchKernelGGL((nc_reduce_hxt_kernel<T>), grid, block, 0, st, (const T*)h, (const T*)x, (const T*)ta, out, s, c, (int)rpb,
-                                          slope, period, parts, (flags & 32) ? 1 : 0));
-    CN_LAUNCH_CHECK();
-    if (parts) {
-        for (int q = 0; q < 3; ++q)
-            if (int e = cn_sum_parts(parts + (size_t)q * sblk * n * c, out + (size_t)q * n * c, sblk, (long)n * c, 0, 1.f, st)) return e;
-    }
-    return CN_OK;
+    const size_t nc = (size_t)n * c;
+    float* const o[3] = {out, out + nc, out + 2 * nc};
+    return nc_reduce_run(o, n, s, c, (flags & 16) != 0, st, [&](const NcReducePlan& p, dim3 grid, dim3 block, float* parts) {
+        CN_DISPATCH_DT(dt, hipLaunchKernelGGL((nc_reduce_hxt_kernel<T>), grid, block, 0, st, (const T*)h, (const T*)x, (const T*)ta, out, s, c,
+                                              p.rows_per_block, slope, period, parts, (flags & 32) ? 1 : 0));
+    });
 }
 
+// out (4, n, c) = sum x, sum x^2, sum lrelu(x), sum lrelu(x)^2 over s: the style statistics and the instance-norm statistics of a
+// DiscrBlock's pre-activation tensor in one pass (c % 4 == 0).  flags bit4: `out` is already zero.
 extern "C" int cn_nc_reduce4(const void* x, float* out, int n, int s, int c, float slope, int flags, int dt, void* stream) {
     CN_CHECK_ARG(x && out && n > 0 && s > 0 && c > 0 && c % 4 == 0 && (dt == CN_F32 || dt == CN_BF16), "nc_reduce4: bad args");
     hipStream_t st = (hipStream_t)stream;
-    const int CG = c / 4;
-    int TX = 1;
-    while (TX < CG && TX < 64) TX <<= 1;
-    const int TY = 256 / TX;
-    const int cblk = cn_cdiv(CG, TX);
-    long want = 512 / ((long)cblk * n);
-    if (cn_det()) {
-        const long cap = (long)(CN_DET_WS_FLOATS / (4 * (size_t)n * c));
-        if (want > cap) want = cap;
-    }
-    if (want < 1) want = 1;
-    if (want > 256) want = 256;
-    long rpb = (s + want - 1) / want;
-    if (rpb < 4 * TY) rpb = 4 * TY;
-    const int sblk = cn_cdiv(s, rpb);
-    float* parts = nullptr;
-    if (cn_det() && sblk > 1) {
-        parts = cn_det_ws(st, 4 * (size_t)sblk * n * c);
-        if (!parts) return CN_EINVAL;
-    } else if (sblk > 1 && !(flags & 16)) {
-        if (int ez__ = cn_zero_async(out, sizeof(float) * 4 * (size_t)n * c, st)) return ez__;
-    }
-    dim3 grid(cblk, sblk, n), block(TX, TY);
-    CN_DISPATCH_DT(dt, hipLaunchKernelGGL((nc_reduce4_kernel<T>), grid, block, 0, st, (const T*)x, out, s, c, (int)rpb, slope, parts));
-    CN_LAUNCH_CHECK();
-    if (parts) {
-        for (int q = 0; q < 4; ++q)
-            if (int e = cn_sum_parts(parts + (size_t)q * sblk * n * c, out + (size_t)q * n * c, sblk, (long)n * c, 0, 1.f, st)) return e;
-    }
-    return CN_OK;
+    const size_t nc = (size_t)n * c;
+    float* const o[4] = {out, out + nc, out + 2 * nc, out + 3 * nc};
+    return nc_reduce_run(o, n, s, c, (flags & 16) != 0, st, [&](const NcReducePlan& p, dim3 grid, dim3 block, float* parts) {
+        CN_DISPATCH_DT(dt, hipLaunchKernelGGL((nc_reduce4_kernel<T>), grid, block, 0, st, (const T*)x, out, s, c, p.rows_per_block, slope, parts));
+    });
 }
 
 extern "C" int cn_nc_reduce(const void* x1, const void* x2, float* s1, float* s2, int n, int s, int c, int flags,
@@ -1232,6 +1158,29 @@ extern "C" int cn_nc_reduce_dact(const void* x1, const void* x2, float* s1, floa
     return nc_reduce_launch(x1, x2, s1, s2, n, s, c, flags, slope, dt, stream, dact_out, act, nullptr, nullptr, nullptr, 1);
 }
 
+// The per-sample "rows" grid of nc_lin2_rows_kernel / norm_apply_rows_kernel: grid (gx, ny) with gx * 256 a multiple of the channel
+// group count CG, so a thread keeps one channel group; G = groups per grid row.  Tensors big enough to care (G >= 16384), ~4 groups
+// per thread, at most ~8192 workgroups, gx a multiple of q = CG / gcd(CG, 256) <= 32.  Pure.
+struct NcRowsPlan { bool rows; unsigned gx; };
+static NcRowsPlan plan_nc_rows(long G, int CG, int ny) {
+    int gcd = CG, r256 = 256;
+    while (r256) { const int t = gcd % r256; gcd = r256; r256 = t; }
+    const int q = CG / gcd;
+    if (!(G >= 16384 && G < 2147483647L - 256 * 8192L && q <= 32)) return {false, 0};
+    long gx = (G + 256 * 4 - 1) / (256 * 4);
+    if (gx * ny > 8192) gx = 8192 / ny;
+    if (gx < 1) gx = 1;
+    return {true, (unsigned)((gx + q - 1) / q * q)};
+}
+
+extern "C" int cn_nc_rows_plan(long long G, int CG, int ny, int out[2]) {
+    CN_CHECK_ARG(G > 0 && CG > 0 && ny > 0 && out, "nc_rows_plan: bad args");
+    const NcRowsPlan p = plan_nc_rows((long)G, CG, ny);
+    out[0] = p.rows;
+    out[1] = (int)p.gx;
+    return CN_OK;
+}
+
 extern "C" int cn_nc_lin2(const void* x1, const float* a1, const void* x2, const float* a2, const float* bb,
                           const float* a3, const float* b3, void* y, int n, int s, int c, int cstride, int flags,
                           float slope, int dt, void* stream) {
@@ -1243,26 +1192,17 @@ extern "C" int cn_nc_lin2(const void* x1, const float* a1, const void* x2, const
     const int period2 = flags >> 8;                 // bits 8..: x2 holds `period2` samples, used for sample n as n % period2
     CN_CHECK_ARG(period2 == 0 || (x2 && cstride && n % period2 == 0), "nc_lin2: bad x2 period %d for n = %d", period2, n);
     flags &= 255;
-    {
-        // big tensors: per-sample grid with a fixed channel group per thread (nc_lin2_rows_kernel)
-        const int CG = c / V;
-        const int ny = cstride ? n : 1;
-        const long G = total / ny;                 // groups per grid row (per_channel: the whole tensor)
-        int gcd = CG, r256 = 256;
-        while (r256) { const int t = gcd % r256; gcd = r256; r256 = t; }
-        const int q = CG / gcd;                    // gx must be a multiple of q
-        if (G >= 16384 && G < 2147483647L - 256 * 8192L && q <= 32) {
-            long gx = (G + 256 * 4 - 1) / (256 * 4);           // ~4 groups per thread
-            if (gx * ny > 8192) gx = 8192 / ny;
-            if (gx < 1) gx = 1;
-            gx = (gx + q - 1) / q * q;
-            CN_DISPATCH_DT(dt, {
-                if (V == 4) hipLaunchKernelGGL((nc_lin2_rows_kernel<4, T>), dim3((unsigned)gx, ny), dim3(256), 0, st, (const T*)x1, a1, (const T*)x2, a2, bb, a3, b3, (T*)y, (int)G, CG, cstride, flags, slope, period2);
-                else hipLaunchKernelGGL((nc_lin2_rows_kernel<1, T>), dim3((unsigned)gx, ny), dim3(256), 0, st, (const T*)x1, a1, (const T*)x2, a2, bb, a3, b3, (T*)y, (int)G, CG, cstride, flags, slope, period2);
-            });
-            CN_LAUNCH_CHECK();
-            return CN_OK;
-        }
+    const int CG = c / V;
+    const int ny = cstride ? n : 1;
+    const long G = total / ny;                     // groups per grid row (per_channel: the whole tensor)
+    const NcRowsPlan rp = plan_nc_rows(G, CG, ny);
+    if (rp.rows) {                                 // big tensors: per-sample grid with a fixed channel group per thread
+        CN_DISPATCH_DT(dt, {
+            if (V == 4) hipLaunchKernelGGL((nc_lin2_rows_kernel<4, T>), dim3(rp.gx, ny), dim3(256), 0, st, (const T*)x1, a1, (const T*)x2, a2, bb, a3, b3, (T*)y, (int)G, CG, cstride, flags, slope, period2);
+            else hipLaunchKernelGGL((nc_lin2_rows_kernel<1, T>), dim3(rp.gx, ny), dim3(256), 0, st, (const T*)x1, a1, (const T*)x2, a2, bb, a3, b3, (T*)y, (int)G, CG, cstride, flags, slope, period2);
+        });
+        CN_LAUNCH_CHECK();
+        return CN_OK;
     }
     CN_DISPATCH_DT(dt, {
         if (V == 4) hipLaunchKernelGGL((nc_lin2_kernel<4, T>), dim3(ew_blocks(total)), dim3(256), 0, st, (const T*)x1, a1, (const T*)x2, a2, bb, a3, b3, (T*)y, total, s, c, cstride, flags, slope, period2);
@@ -1290,19 +1230,12 @@ extern "C" int cn_norm_apply(int mode, int dir, const void* x1, const void* x2, 
     flags &= 255;
     const int CG = c / 4;
     const long G = (long)s * CG;
-    int gcd = CG, r256 = 256;
-    while (r256) { const int t = gcd % r256; gcd = r256; r256 = t; }
-    const int q = CG / gcd;
-    if (!(G >= 16384 && G < 2147483647L - 256 * 8192L && q <= 32)) return CN_EUNSUPPORTED;
-    long gx = (G + 256 * 4 - 1) / (256 * 4);
-    if (gx * n > 8192) gx = 8192 / n;
-    if (gx < 1) gx = 1;
-    gx = (gx + q - 1) / q * q;
-    if (gx * 256 < CG) return CN_EUNSUPPORTED;          // (workgroup column 0 must cover every channel group: it writes the side outputs)
+    const NcRowsPlan rp = plan_nc_rows(G, CG, n);
+    if (!rp.rows || (long)rp.gx * 256 < CG) return CN_EUNSUPPORTED;     // (workgroup column 0 must cover every channel group: it writes the side outputs)
     NormApplyArgs A;
     A.mode = mode; A.dir = dir; A.N = n; A.C = c; A.invS = 1.f / (float)s; A.eps = eps;
     A.s1 = sa; A.s2 = sb; A.p1 = p1; A.p2 = p2; A.sm = save_mean; A.sr = save_r; A.gp1 = gp1; A.gp2 = gp2;
-    CN_DISPATCH_DT(dt, hipLaunchKernelGGL((norm_apply_rows_kernel<T>), dim3((unsigned)gx, n), dim3(256), 0, (hipStream_t)stream, A, (const T*)x1,
+    CN_DISPATCH_DT(dt, hipLaunchKernelGGL((norm_apply_rows_kernel<T>), dim3(rp.gx, n), dim3(256), 0, (hipStream_t)stream, A, (const T*)x1,
                                           (const T*)x2, a3, b3, (T*)y, (int)G, CG, flags, slope, period2));
     CN_LAUNCH_CHECK();
     return CN_OK;

@@ -53,6 +53,19 @@ def _partial_rows(rows):
     return next(r for r in (16, 8, 4, 2, 1) if rows % r == 0)
 
 
+def _spread(x):
+    """(rep, s, c): x (..., c) seen as `rep` partial rows (_partial_rows) of s rows each."""
+    c = x.shape[-1]
+    rows = x.numel() // c
+    rep = _partial_rows(rows)
+    return rep, rows // rep, c
+
+
+def _readd(t, rep, dim):
+    """The partial rows of _spread (axis `dim` of t, kept with extent 1) added again."""
+    return t.sum(dim, keepdim=True) if rep > 1 else t
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -795,6 +808,15 @@ def zero_pool_alloc(shape, device):
     return out
 
 
+def _sums(shape, device):
+    """(fp32 sums of a reduction, flag): carved from the step's zero pool (16: already clear) or fresh (0: the call clears them
+    where its kernel adds with atomics)."""
+    t = zero_pool_alloc(shape, device)
+    if t is not None:
+        return t, 16
+    return torch.empty(shape, device=device, dtype=torch.float32), 0
+
+
 def zero_(t):
     """Clear a contiguous fp32 tensor with the library's own kernel (a graph node that re-executes on replay)."""
     check(lib.cn_zero(_fptr(t), t.numel() * 4, _stream()), "cn_zero")
@@ -853,40 +875,20 @@ def nc_reduce(x1, x2=None, want_sum=True, want_dot=True, flags=0, slope=0.0, per
     if per_channel:
         # every workgroup ends in one atomic per channel: spread a long reduction over `rep` partial rows (as if
         # they were samples) so that no address takes more than ~128 of them, then add the partials
-        rows = n * s
-        rep = _partial_rows(rows)
-        n, s = rep, rows // rep
-    if want_sum and want_dot:           # adjacent outputs: cleared by one launch (or by the step's zero pool)
-        s12 = zero_pool_alloc((2, n, c), x1.device)
-        if s12 is not None:
-            flags |= 16
-        else:
-            s12 = torch.empty((2, n, c), device=x1.device, dtype=torch.float32)
-        s1, s2 = s12[0], s12[1]
-    else:
-        one = zero_pool_alloc((n, c), x1.device)
-        if one is not None:
-            flags |= 16
-        else:
-            one = torch.empty((n, c), device=x1.device, dtype=torch.float32)
-        s1, s2 = (one, None) if want_sum else (None, one)
-    check(lib.cn_nc_reduce(_ptr(x1), _ptr(x2), _ptr(s1), _ptr(s2), n, s, c, flags, slope, _dt(x1), _stream()), "cn_nc_reduce")
-    if rep > 1:
-        if want_sum and want_dot:
-            s12 = s12.sum(1, keepdim=True)
-            return s12[0], s12[1]
-        s1 = s1.sum(0, keepdim=True) if s1 is not None else None
-        s2 = s2.sum(0, keepdim=True) if s2 is not None else None
-    return s1, s2
+        rep, s, c = _spread(x1)
+        n = rep
+    # (both sums: adjacent outputs, cleared by one launch or by the step's zero pool)
+    sums, flag = _sums((int(want_sum) + int(want_dot), n, c), x1.device)
+    s1, s2 = (sums[0] if want_sum else None), (sums[-1] if want_dot else None)
+    check(lib.cn_nc_reduce(_ptr(x1), _ptr(x2), _ptr(s1), _ptr(s2), n, s, c, flags | flag, slope, _dt(x1), _stream()), "cn_nc_reduce")
+    sums = _readd(sums, rep, 1)
+    return (sums[0] if want_sum else None), (sums[-1] if want_dot else None)
 
 
 def nc_reduce4(x, slope):
     """(sum x, sum x^2, sum l, sum l^2) per (n, c) with l = leaky_relu(x, slope): cn_nc_reduce4 (one pass instead of two)."""
     n, s, c = _nsc(x)
-    out = zero_pool_alloc((4, n, c), x.device)
-    flags = 16
-    if out is None:
-        out, flags = torch.empty((4, n, c), device=x.device, dtype=torch.float32), 0
+    out, flags = _sums((4, n, c), x.device)
     check(lib.cn_nc_reduce4(_ptr(x), _ptr(out), n, s, c, slope, flags, _dt(x), _stream()), "cn_nc_reduce4")
     return out[0], out[1], out[2], out[3]
 
@@ -1083,11 +1085,9 @@ def nc_reduce_hxt(h, x, ta, slope, ta_is_tx=False):
     ta_is_tx: `ta` is the tangent input tx, ta = lrelu'(x) tx is formed in the pass."""
     h, x, ta = _unify(h, x, ta)
     n, s, c = _nsc(h)
-    out = zero_pool_alloc((3, n, c), h.device)
-    flags = 16 | (32 if ta_is_tx else 0)
-    if out is None:
-        out, flags = torch.empty((3, n, c), device=h.device, dtype=torch.float32), flags & 32
-    check(lib.cn_nc_reduce_hxt(_ptr(h), _ptr(x), _ptr(ta), _ptr(out), n, s, c, slope, x.shape[0], flags, _dt(h), _stream()), "cn_nc_reduce_hxt")
+    out, flags = _sums((3, n, c), h.device)
+    check(lib.cn_nc_reduce_hxt(_ptr(h), _ptr(x), _ptr(ta), _ptr(out), n, s, c, slope, x.shape[0], flags | (32 if ta_is_tx else 0), _dt(h),
+                               _stream()), "cn_nc_reduce_hxt")
     return out[0], out[1], out[2]
 
 
@@ -1096,21 +1096,13 @@ def bn_act_bwd(gy, y, x, a, act, want_g):
     per-channel parameter sums in one pass over gy / y / x."""
     gy, y, x = _unify(gy, y, x)
     _log_mask(y, act)
-    c = gy.shape[-1]
-    rows = gy.numel() // c
-    rep = _partial_rows(rows)
+    rep, s, c = _spread(gy)
     gx = torch.empty_like(gy)
     g = torch.empty_like(gy) if want_g else None
-    s12 = zero_pool_alloc((2, rep, c), gy.device)
-    flags = 16
-    if s12 is None:
-        s12, flags = torch.empty((2, rep, c), device=gy.device, dtype=torch.float32), 0
-    check(lib.cn_bn_act_bwd(_ptr(gy), _ptr(y), _ptr(x), _fptr(_c(a)), _ptr(g), _ptr(gx), _ptr(s12[0]), _ptr(s12[1]), rep, rows // rep, c,
+    s12, flags = _sums((2, rep, c), gy.device)
+    check(lib.cn_bn_act_bwd(_ptr(gy), _ptr(y), _ptr(x), _fptr(_c(a)), _ptr(g), _ptr(gx), _ptr(s12[0]), _ptr(s12[1]), rep, s, c,
                             act, flags, _dt(gy), _stream()), "cn_bn_act_bwd")
-    if rep > 1:
-        s12 = s12.sum(1)
-    else:
-        s12 = s12.reshape(2, c)
+    s12 = _readd(s12, rep, 1).reshape(2, c)
     return gx, g, s12[0], s12[1]
 
 
@@ -1121,14 +1113,9 @@ def nc_reduce_dact(x1, x2, act, slope, x2_period=0, flags=0, want_dot=True, want
     _log_mask(x2, act)
     n, s, c = _nsc(x1)
     a = torch.empty_like(x1) if want_a else None
-    flags |= x2_period << 8
-    s12 = zero_pool_alloc((2, n, c), x1.device)
-    if s12 is not None:
-        flags |= 16
-    else:
-        s12 = torch.empty((2, n, c), device=x1.device, dtype=torch.float32)
-    check(lib.cn_nc_reduce_dact(_ptr(x1), _ptr(x2), _ptr(s12[0]), _ptr(s12[1]) if want_dot else None, _ptr(a), n, s, c, flags, slope,
-                                act, _dt(x1), _stream()), "cn_nc_reduce_dact")
+    s12, flag = _sums((2, n, c), x1.device)
+    check(lib.cn_nc_reduce_dact(_ptr(x1), _ptr(x2), _ptr(s12[0]), _ptr(s12[1]) if want_dot else None, _ptr(a), n, s, c,
+                                flags | flag | x2_period << 8, slope, act, _dt(x1), _stream()), "cn_nc_reduce_dact")
     return a, s12[0], (s12[1] if want_dot else None)
 
 
@@ -1177,15 +1164,10 @@ def act_bwd_partials(gy, y, act, slope=0.0):
     (cn_act_bwd_bias); the caller adds the slices (sum_rows_into)."""
     gy, y = _unify(gy, y)
     _log_mask(y, act)
-    _, _, c = _nsc(gy)
-    rows = gy.numel() // c
-    rep = _partial_rows(rows)                       # as nc_reduce(per_channel=True)
+    rep, s, c = _spread(gy)                          # as nc_reduce(per_channel=True)
     gx = torch.empty_like(gy)
-    gb = zero_pool_alloc((rep, c), gy.device)
-    flags = 16
-    if gb is None:
-        gb, flags = torch.empty((rep, c), device=gy.device, dtype=torch.float32), 0
-    check(lib.cn_act_bwd_bias(_ptr(gy), _ptr(y), _ptr(gx), _ptr(gb), rep, rows // rep, c, act, slope, flags, _dt(gy), _stream()),
+    gb, flags = _sums((rep, c), gy.device)
+    check(lib.cn_act_bwd_bias(_ptr(gy), _ptr(y), _ptr(gx), _ptr(gb), rep, s, c, act, slope, flags, _dt(gy), _stream()),
           "cn_act_bwd_bias")
     return gx, gb
 
@@ -1194,11 +1176,10 @@ def act_bwd_bias(gy, y, act, slope=0.0, sink=None):
     """(gx, gb): act_bwd fused with the per-channel sum of its result (the bias gradient) -- one pass instead of two.
     sink: the bias's slot of a gradient arena (grad_sink) -- the sum is ADDED there and gb is returned as None."""
     gx, gb = act_bwd_partials(gy, y, act, slope)
-    rep = gb.shape[0]
     if sink is not None:
         sum_rows_into(gb, sink)
         return gx, None
-    return gx, (gb.sum(0) if rep > 1 else gb.reshape(-1))
+    return gx, _readd(gb, gb.shape[0], 0).reshape(-1)
 
 
 def sum_rows_into(partial, dst, accumulate=True, defer=True):
@@ -1221,19 +1202,14 @@ def bias_grad(gy, sink=None):
     gy = _c(gy)
     if sink is None:
         return nc_reduce(gy, None, want_dot=False, per_channel=True)[0].reshape(-1)
-    c = gy.shape[-1]
-    rows = gy.numel() // c
-    if rows <= 64 and gy.dtype == torch.float32 and _SINK is not None:
+    rep, s, c = _spread(gy)
+    if rep * s <= 64 and gy.dtype == torch.float32 and _SINK is not None:
         # a dense layer's bias gradient over a batch of a few rows: the rows ARE the slabs of the pass' grouped reduction
         # (grad_sink.join) -- no launch of its own
-        sum_rows_into(gy.reshape(rows, c), sink)
+        sum_rows_into(gy.reshape(s, c), sink)
         return None
-    rep = _partial_rows(rows)
-    part = zero_pool_alloc((rep, c), gy.device)
-    flags = 16
-    if part is None:
-        part, flags = torch.empty((rep, c), device=gy.device, dtype=torch.float32), 0
-    check(lib.cn_nc_reduce(_ptr(gy), None, _ptr(part), None, rep, rows // rep, c, flags, 0.0, _dt(gy), _stream()), "cn_nc_reduce")
+    part, flags = _sums((rep, c), gy.device)
+    check(lib.cn_nc_reduce(_ptr(gy), None, _ptr(part), None, rep, s, c, flags, 0.0, _dt(gy), _stream()), "cn_nc_reduce")
     sum_rows_into(part, sink)
     return None
 

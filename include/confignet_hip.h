@@ -302,9 +302,18 @@ int cn_sum_rows_into(const float* src, float* dst, int rows, int cols, int accum
  * (keras ResNet50), global average pooling and every bias gradient.
  *   a = f1(x1), b = x2 ? f2(x2) : a ;  sum1[n,c] = sum_s a ; sum2[n,c] = sum_s a*b
  *   flags: bit0 leaky-relu(slope) on x1, bit1 leaky-relu(slope) on x2, bit4: the outputs are already zero
- *   (skip the clearing launch); bits 8..: x2 holds only (flags >> 8) samples and sample n reads x2[n % period] (the batched
+ *   (no clearing launch); bits 8..: x2 holds only (flags >> 8) samples and sample n reads x2[n % period] (the batched
  *   R1 input-gradient pass stacks the cotangents of several heads along n against ONE copy of the activations).
- *   Outputs are overwritten. */
+ *   Outputs are overwritten.
+ * cn_nc_reduce, cn_nc_reduce4, cn_nc_reduce_hxt, cn_nc_reduce_dact, cn_bn_act_bwd and cn_act_bwd_bias share ONE launch rule
+ * and one launcher: 256 threads as TX channel groups (4 channels each where c % 4 == 0, else 1) x TY rows, grid (channel
+ * blocks, row blocks, n) with ~512 workgroups, at most 256 row blocks and at least 4 TY rows per block.  One row block: plain
+ * stores.  More: fp32 atomics into outputs that are cleared first UNLESS bit4 says they are clear -- the only clearing launch there
+ * is --, or in deterministic mode per-row-block partials added in block order (cn_set_deterministic). */
+/* Diagnostic: that rule for nsums (1..4) sums of an (n, s, c) tensor, decided by the function the calls decide with, without a
+ * device.  out = {channels per thread, TX, TY, channel blocks, row blocks, rows per block, outputs cleared first (0 / 1), floats of
+ * the deterministic workspace}. */
+int cn_nc_reduce_plan(int n, int s, int c, int nsums, int prezeroed, int det, int out[8]);
 /* The four statistics of a DiscrBlock's tail (building_blocks.py:97-106) in ONE pass over its pre-activation tensor:
  * out (4, n, c) = sum x, sum x^2 (get_layer_style of the pre-activation), sum l, sum l^2 with l = leaky_relu(x, slope) (the
  * InstanceNormalization behind the activation); c % 4 == 0; flags bit4: `out` is already zero. */
@@ -331,6 +340,12 @@ int cn_bn_act_bwd(const void* gy, const void* y, const void* x, const float* a, 
 int cn_nc_lin2(const void* x1, const float* a1, const void* x2, const float* a2, const float* bb,
                const float* a3, const float* b3, void* y, int n, int s, int c, int cstride, int flags,
                float slope, int dt, void* stream);
+/* Diagnostic: the per-sample grid of cn_nc_lin2 / cn_norm_apply for G channel groups per grid row, CG channel groups and ny grid
+ * rows (n, or 1 with per-channel coefficients), as the calls decide it.  out = {1: grid (gx, ny), every thread keeps one channel
+ * group / 0: cn_nc_lin2 takes its generic kernel, cn_norm_apply returns CN_EUNSUPPORTED; gx}.  The grid needs G >= 16384 and
+ * CG / gcd(CG, 256) <= 32 (gx is a multiple of it); ~4 groups per thread, ~8192 workgroups at most.  cn_norm_apply also refuses
+ * c % 4 != 0 and gx * 256 < CG. */
+int cn_nc_rows_plan(long long G, int CG, int ny, int out[2]);
 
 /* Per-(n,c) coefficient kernels of the normalisation layers (tiny: N*C threads).
  * mode 0 AdaIN (building_blocks.py:132-144): p1 = [s|b] (N,2C); mu = s1/S, var = s2/S - mu^2,

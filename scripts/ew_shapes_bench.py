@@ -1,6 +1,6 @@
 """Collect every nc_reduce / nc_lin2 launch of one second-stage iteration (256x256, batch 16), time each distinct
 (shape, operands, flags) in isolation (20 launches back to back in a replayed graph) and report achieved GB/s against the bytes
-the launch must move."""
+the launch must move.  --shapes FILE: only write the distinct calls to FILE (tests/golden/nc_plans.json holds that list)."""
 import sys
 from collections import OrderedDict
 
@@ -46,6 +46,11 @@ torch.cuda.synchronize()
 ops.nc_reduce, ops.nc_lin2 = o_red, o_lin
 del m
 torch.cuda.empty_cache()
+if "--shapes" in sys.argv:      # --shapes FILE: write the distinct calls (no timing) as JSON and stop
+    import json
+    with open(sys.argv[sys.argv.index("--shapes") + 1], "w") as f:
+        json.dump([[k[0], list(k[1])] + [int(v) for v in k[2:]] + [cnt] for k, cnt in calls.items()], f)
+    sys.exit(0)
 
 
 def timeit(fn, inner=20, reps=5):
