@@ -99,6 +99,7 @@ SIGNATURES = {
     "cn_conv_wino4_filter": [_p, _p, _i, _i, _i, _p],
     "cn_sumpool2": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     "cn_gemm": [_i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _i, _f, _p],
+    "cn_gemm_plan": [_i] * 10 + [ctypes.POINTER(ctypes.c_int * 9)],
     "cn_nc_reduce4": [_p, _p, _i, _i, _i, _f, _i, _i, _p],
     "cn_nc_reduce": [_p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _p],
     "cn_nc_reduce_plan": [_i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int * 8)],

@@ -369,45 +369,55 @@ __global__ void zero_rows_kernel(float* C, int M, int N, int ldc) {
 
 }  // namespace
 
-static int gemm_launch(int ta, int tb, int m, int n, int k, const float* a, int lda, const float* b, int ldb, float* c,
-                       int ldc, const float* bias, int act, float slope, int accumulate, void* stream) {
-    CN_CHECK_ARG(m > 0 && n > 0 && k > 0 && a && b && c, "gemm: bad args m=%d n=%d k=%d", m, n, k);
-    CN_CHECK_ARG(lda >= (ta ? m : k) && ldb >= (tb ? k : n) && ldc >= n, "gemm: leading dimension too small");
-    hipStream_t s = (hipStream_t)stream;
-    if (!accumulate && !ta && m <= 32 && n > 4 && (long)(m <= 8 ? 8 : m <= 16 ? 16 : 32) * k <= 8192) {
-        const int mt = m <= 8 ? 8 : m <= 16 ? 16 : 32;
-        const size_t lds = sizeof(float) * ((size_t)mt * k + 3 * mt * 64);
-        dim3 grid(cn_cdiv(n, 64));
-#define ROWS(MT_, TB_) hipLaunchKernelGGL((gemm_rows_kernel<MT_, TB_>), grid, dim3(256), lds, s, m, n, k, a, lda, b, ldb, c, ldc, bias, act, slope)
-        if (mt == 8) { if (tb) ROWS(8, true); else ROWS(8, false); }
-        else if (mt == 16) { if (tb) ROWS(16, true); else ROWS(16, false); }
-        else { if (tb) ROWS(32, true); else ROWS(32, false); }
-#undef ROWS
-        CN_LAUNCH_CHECK();
-        return CN_OK;
+// ---- the launch of a dense product: decided here, performed by gemm_launch ----
+enum { GEMM_ROWS = 0, GEMM_DEPTH, GEMM_THIN, GEMM_TILE };
+struct GemmPlan {
+    int route;                // GEMM_ROWS / GEMM_DEPTH / GEMM_THIN / GEMM_TILE
+    int mt;                   // rows: the row count the kernel is instantiated for (8 / 16 / 32); else 0
+    int gx, gy, gz;           // grid
+    int kps;                  // K per slice (thin: grid y slices, tile: grid z slices; rows / depth: k)
+    int zero_first;           // the slices add with atomics: clear C before the launch
+    long parts_floats;        // deterministic mode: the per-slice slabs [gz][m][n] of the stream's workspace, added in order afterwards
+    size_t lds;               // dynamic LDS bytes (rows: the A block [mt][k], then the partial sums [3][mt][64])
+};
+
+// the rows kernels' instantiation for m rows and their LDS block; mt * k <= 8192 floats is what they take
+static inline int gemm_rows_mt(int m) { return m <= 8 ? 8 : m <= 16 ? 16 : 32; }
+static inline size_t gemm_rows_lds(int mt, int k) { return sizeof(float) * ((size_t)mt * k + 3 * mt * 64); }
+
+// Pure.  The order of the tests matters: rows before depth before thin, the 64x64 tile takes what is left.
+static GemmPlan plan_gemm(int ta, int tb, int m, int n, int k, int ldc, bool has_bias, int act, bool accumulate, bool det) {
+    GemmPlan p{};
+    p.gx = p.gy = p.gz = 1;
+    p.kps = k;
+    if (!accumulate && !ta && m <= 32 && n > 4 && (long)gemm_rows_mt(m) * k <= 8192) {
+        p.route = GEMM_ROWS;
+        p.mt = gemm_rows_mt(m);
+        p.lds = gemm_rows_lds(p.mt, k);
+        p.gx = cn_cdiv(n, 64);
+        return p;
     }
-    if (ta && !tb && k <= 32 && !bias && act == CN_ACT_NONE) {
-        dim3 grid(cn_cdiv(m, 16), cn_cdiv(n, 64));
-        hipLaunchKernelGGL(gemm_depth_kernel, grid, dim3(256), 0, s, m, n, k, a, lda, b, ldb, c, ldc, accumulate);
-        CN_LAUNCH_CHECK();
-        return CN_OK;
+    if (ta && !tb && k <= 32 && !has_bias && act == CN_ACT_NONE) {
+        p.route = GEMM_DEPTH;
+        p.gx = cn_cdiv(m, 16);
+        p.gy = cn_cdiv(n, 64);
+        return p;
     }
     if (!accumulate && !ta && !tb && n <= 4 && m <= 256 && k >= 128) {
         int slices = 1;
-        if (act == CN_ACT_NONE && k >= 8192 && !cn_det()) slices = k / 4096;      // (deterministic mode: no K slices, no atomics)
+        if (act == CN_ACT_NONE && k >= 8192 && !det) slices = k / 4096;      // (deterministic mode: no K slices, no atomics)
         const int kps = (k + slices - 1) / slices;
         slices = (k + kps - 1) / kps;
-        if (slices > 1) {
-            hipLaunchKernelGGL(zero_rows_kernel, dim3(cn_cdiv((long)m * n, 256)), dim3(256), 0, s, c, m, n, ldc);
-            CN_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(thin_gemm_kernel, dim3(m, slices), dim3(256), 0, s, m, n, k, a, lda, b, ldb, c, ldc, bias, act, slope, kps);
-        CN_LAUNCH_CHECK();
-        return CN_OK;
+        p.route = GEMM_THIN;
+        p.gx = m;
+        p.gy = slices;
+        p.kps = kps;
+        p.zero_first = slices > 1;
+        return p;
     }
     const long tiles = (long)cn_cdiv(m, 64) * cn_cdiv(n, 64);
     int splitk = 1;
-    if (act == CN_ACT_NONE && tiles < 128 && k >= 1024 && !(cn_det() && (accumulate || ldc != n))) {
+    if (act == CN_ACT_NONE && tiles < 128 && k >= 1024 && !(det && (accumulate || ldc != n))) {
         splitk = (int)((256 + tiles - 1) / tiles);
         if (splitk > k / 256) splitk = k / 256;
         if (splitk < 1) splitk = 1;
@@ -415,29 +425,75 @@ static int gemm_launch(int ta, int tb, int m, int n, int k, const float* a, int 
     int kps = (k + splitk - 1) / splitk;
     kps = (kps + BK - 1) / BK * BK;
     splitk = (k + kps - 1) / kps;
-    float* parts = nullptr;
-    if (cn_det() && splitk > 1) {
-        // deterministic mode: K slices into per-split slabs of the stream's workspace, added in split order by a second launch
+    if (det && splitk > 1) {
+        // deterministic mode: K slices into per-split slabs of the stream's workspace, added in split order by a second launch.
+        // The cap never binds: splitting needs tiles < 128, so m * n <= 4096 * tiles and cap >= 4096 / tiles, while the split asked
+        // for is at most ceil(256 / tiles) (tests/test_gemm_plan_cpu.py sweeps it); it stays as the guard of the workspace size.
         const long cap = (long)(CN_DET_WS_FLOATS / ((size_t)m * n));
         if (splitk > cap) splitk = (int)(cap < 1 ? 1 : cap);
         kps = (k + splitk - 1) / splitk;
         kps = (kps + BK - 1) / BK * BK;
         splitk = (k + kps - 1) / kps;
-        if (splitk > 1) {
-            parts = cn_det_ws(s, (size_t)splitk * m * n);
-            if (!parts) return CN_EINVAL;
-        }
+        if (splitk > 1) p.parts_floats = (long)splitk * m * n;
     }
-    if (splitk > 1 && !accumulate && !parts) {
+    p.route = GEMM_TILE;
+    p.gx = cn_cdiv(m, 64);
+    p.gy = cn_cdiv(n, 64);
+    p.gz = splitk;
+    p.kps = kps;
+    p.zero_first = splitk > 1 && !accumulate && !p.parts_floats;
+    return p;
+}
+
+/* out = {route (0 rows, 1 depth, 2 thin, 3 tile), MT of the rows kernel (else 0), grid x, y, z, K per slice, C cleared first (0 / 1),
+ * floats of the deterministic workspace, dynamic LDS bytes} */
+extern "C" int cn_gemm_plan(int ta, int tb, int m, int n, int k, int ldc, int has_bias, int act, int accumulate, int deterministic,
+                            int out[9]) {
+    CN_CHECK_ARG(m > 0 && n > 0 && k > 0 && ldc >= n && out, "gemm_plan: bad args m=%d n=%d k=%d ldc=%d", m, n, k, ldc);
+    const GemmPlan p = plan_gemm(ta, tb, m, n, k, ldc, has_bias != 0, act, accumulate != 0, deterministic != 0);
+    const int v[9] = {p.route, p.mt, p.gx, p.gy, p.gz, p.kps, p.zero_first, (int)p.parts_floats, (int)p.lds};
+    for (int i = 0; i < 9; ++i) out[i] = v[i];
+    return CN_OK;
+}
+
+// Performs the plan: deterministic workspace, zero pass, the launch, the ordered sum of the slabs.
+static int gemm_launch(int ta, int tb, int m, int n, int k, const float* a, int lda, const float* b, int ldb, float* c,
+                       int ldc, const float* bias, int act, float slope, int accumulate, void* stream) {
+    CN_CHECK_ARG(m > 0 && n > 0 && k > 0 && a && b && c, "gemm: bad args m=%d n=%d k=%d", m, n, k);
+    CN_CHECK_ARG(lda >= (ta ? m : k) && ldb >= (tb ? k : n) && ldc >= n, "gemm: leading dimension too small");
+    hipStream_t s = (hipStream_t)stream;
+    const GemmPlan p = plan_gemm(ta, tb, m, n, k, ldc, bias != nullptr, act, accumulate != 0, cn_det() != 0);
+    float* parts = nullptr;
+    if (p.parts_floats) {
+        parts = cn_det_ws(s, (size_t)p.parts_floats);
+        if (!parts) return CN_EINVAL;
+    }
+    if (p.zero_first) {
         hipLaunchKernelGGL(zero_rows_kernel, dim3(cn_cdiv((long)m * n, 256)), dim3(256), 0, s, c, m, n, ldc);
         CN_LAUNCH_CHECK();
     }
-    dim3 grid(cn_cdiv(m, 64), cn_cdiv(n, 64), splitk);
-    // (the kernel adds with atomics whenever its last argument is > 1: split-K, or accumulation into the caller's C)
-    hipLaunchKernelGGL(gemm_kernel, grid, dim3(256), 0, s, ta, tb, m, n, k, a, lda, b, ldb, c, ldc, bias, act, slope, kps,
-                       accumulate ? 2 : splitk, parts);
+    const dim3 grid(p.gx, p.gy, p.gz);
+    switch (p.route) {
+        case GEMM_ROWS:
+#define ROWS(MT_, TB_) hipLaunchKernelGGL((gemm_rows_kernel<MT_, TB_>), grid, dim3(256), p.lds, s, m, n, k, a, lda, b, ldb, c, ldc, bias, act, slope)
+            if (p.mt == 8) { if (tb) ROWS(8, true); else ROWS(8, false); }
+            else if (p.mt == 16) { if (tb) ROWS(16, true); else ROWS(16, false); }
+            else { if (tb) ROWS(32, true); else ROWS(32, false); }
+#undef ROWS
+            break;
+        case GEMM_DEPTH:
+            hipLaunchKernelGGL(gemm_depth_kernel, grid, dim3(256), 0, s, m, n, k, a, lda, b, ldb, c, ldc, accumulate);
+            break;
+        case GEMM_THIN:
+            hipLaunchKernelGGL(thin_gemm_kernel, grid, dim3(256), 0, s, m, n, k, a, lda, b, ldb, c, ldc, bias, act, slope, p.kps);
+            break;
+        default:
+            // (the kernel adds with atomics whenever its last but one argument is > 1: split-K, or accumulation into the caller's C)
+            hipLaunchKernelGGL(gemm_kernel, grid, dim3(256), 0, s, ta, tb, m, n, k, a, lda, b, ldb, c, ldc, bias, act, slope, p.kps,
+                               accumulate ? 2 : p.gz, parts);
+    }
     CN_LAUNCH_CHECK();
-    if (parts) return cn_sum_parts(parts, c, splitk, (long)m * n, 0, 1.f, s);
+    if (parts) return cn_sum_parts(parts, c, p.gz, (long)m * n, 0, 1.f, s);
     return CN_OK;
 }
 
@@ -476,9 +532,9 @@ extern "C" int cn_gemm_rows_grouped(const CnRowsJob* jobs, int njobs, void* stre
         }
         J.blk0[cnt] = (int)blocks;
         J.count = cnt;
-        const int mt = mmax <= 8 ? 8 : mmax <= 16 ? 16 : 32;
+        const int mt = gemm_rows_mt(mmax);
         CN_CHECK_ARG((long)mt * kmax <= 8192, "cn_gemm_rows_grouped: %d rows x k = %d do not fit the LDS block", mt, kmax);
-        const size_t lds = sizeof(float) * ((size_t)mt * kmax + 3 * mt * 64);
+        const size_t lds = gemm_rows_lds(mt, kmax);
         if (mt == 8) hipLaunchKernelGGL((gemm_rows_grouped_kernel<8>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, J);
         else if (mt == 16) hipLaunchKernelGGL((gemm_rows_grouped_kernel<16>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, J);
         else hipLaunchKernelGGL((gemm_rows_grouped_kernel<32>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, J);

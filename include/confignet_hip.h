@@ -275,6 +275,13 @@ int cn_cast(const void* src, int src_dt, void* dst, int dst_dt, size_t numel, vo
 int cn_gemm(int trans_a, int trans_b, int m, int n, int k, const float* a, int lda,
             const float* b, int ldb, float* c, int ldc, const float* bias, int act, float slope,
             void* stream);
+/* Diagnostic: the launch cn_gemm (accumulate = 0) or cn_gemm_acc (accumulate = 1; has_bias = 0, act = CN_ACT_NONE) gets for this request,
+ * decided by the function the calls decide with, without a device.  deterministic: plan as in deterministic mode.  out = {route (0: m <= 32
+ * rows with the A block in LDS, 1: A^T B with k <= 32, 2: n <= 4 with K slices, 3: the 64x64 MFMA tile), rows per workgroup of route 0
+ * (8 / 16 / 32; else 0), grid x, y, z, K per slice (route 2: grid y slices, route 3: grid z slices), C cleared first (0 / 1: the slices
+ * add with atomics), floats of the deterministic workspace (route 3: grid z slabs of m x n, added in order afterwards), dynamic LDS bytes}. */
+int cn_gemm_plan(int trans_a, int trans_b, int m, int n, int k, int ldc, int has_bias, int act, int accumulate, int deterministic,
+                 int out[9]);
 
 /* Deterministic mode (process-wide; switch between steps, not inside a captured graph): with on != 0 every reduction of the
  * fp32 path runs in a fixed order -- statistics passes, split-K of cn_conv_fwd / cn_gemm, filter gradients and loss reductions
