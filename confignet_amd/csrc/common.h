@@ -131,6 +131,14 @@ __device__ __forceinline__ float cn_apply_act(float v, int act, float slope) {
     return v;
 }
 
+// derivative of an activation evaluated from its OUTPUT o
+__device__ __forceinline__ float act_deriv(float o, int act, float slope) {
+    if (act == CN_ACT_LRELU) return o > 0.f ? 1.f : slope;
+    if (act == CN_ACT_RELU) return o > 0.f ? 1.f : 0.f;
+    if (act == CN_ACT_TANH) return 1.f - o * o;
+    return 1.f;
+}
+
 static inline int cn_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // compute units of the current device (hipDeviceAttributeMultiprocessorCount, read once; 256 on an MI355X): the launch cost models

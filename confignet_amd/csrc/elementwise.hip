@@ -10,14 +10,6 @@ namespace {
 
 __device__ __forceinline__ float lrelu(float v, float s) { return v > 0.f ? v : v * s; }
 
-// derivative of an activation evaluated from its OUTPUT o
-__device__ __forceinline__ float act_deriv(float o, int act, float slope) {
-    if (act == CN_ACT_LRELU) return o > 0.f ? 1.f : slope;
-    if (act == CN_ACT_RELU) return o > 0.f ? 1.f : 0.f;
-    if (act == CN_ACT_TANH) return 1.f - o * o;
-    return 1.f;
-}
-
 // ---- (N,S,C) -> (N,C) reductions: ONE row walk (nc_reduce_rows), three operand sets (NcSumDot, NcStats4, NcHxt) ----
 // grid (cblk, sblk, n); block (TX channel groups, TY rows): plan_nc_reduce below.  An operand set supplies begin() (the addresses
 // of one (sample, channel group)), load<U>() (U rows of every array it reads: all rows of one array, then the next array) and add()
@@ -721,6 +713,33 @@ __global__ void maxpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, i
     }
 }
 
+// The same pool on 4-channel groups with 32-bit index arithmetic (as maxpool_bwd4_kernel): one 16-byte read per window cell, one 16-byte
+// write.  Same window scan, same fmaxf chain and the same padding rule (a zero-padding cell takes part only when pad > 0).
+template <typename T>
+__global__ void maxpool_fwd4_kernel(const T* __restrict__ x, T* __restrict__ y, int n, int h, int w, int c4,
+                                    int oh, int ow, int k, int s, int pad) {
+    const int total = n * oh * ow * c4;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const int cg = i % c4;
+        int t = i / c4;
+        const int ox = t % ow;
+        t /= ow;
+        const int oy = t % oh;
+        const int b = t / oh;
+        float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        for (int dy = 0; dy < k; ++dy)
+            for (int dx = 0; dx < k; ++dx) {
+                const int iy = oy * s - pad + dy, ix = ox * s - pad + dx;
+                const bool in = iy >= 0 && iy < h && ix >= 0 && ix < w;
+                if (!in && pad == 0) continue;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (in) v = ld4<T>(x + ((long)(b * h + iy) * w + ix) * c4 * 4 + cg * 4);
+                best[0] = fmaxf(best[0], v.x); best[1] = fmaxf(best[1], v.y); best[2] = fmaxf(best[2], v.z); best[3] = fmaxf(best[3], v.w);
+            }
+        st4<T>(y + (long)i * 4, make_float4(best[0], best[1], best[2], best[3]));
+    }
+}
+
 // AveragePooling2D((3, 3), strides 1, padding "same") [TF-2.1]: the mean over the window cells INSIDE the image (tf.nn.avg_pool
 // does not count padding), float4 over channels.  InceptionV3's pool branches (metrics path).
 template <int V, typename T>
@@ -1360,6 +1379,12 @@ extern "C" int cn_maxpool_fwd(const void* x, void* y, int n, int h, int w, int c
     CN_CHECK_ARG(x && y && n > 0 && h > 0 && w > 0 && c > 0 && k > 0 && s > 0 && pad >= 0 && (dt == CN_F32 || dt == CN_BF16), "maxpool: bad args");
     const int oh = (h + 2 * pad - k) / s + 1, ow = (w + 2 * pad - k) / s + 1;
     const size_t total = (size_t)n * oh * ow * c;
+    if (c % 4 == 0 && alv(x, dt) && alv(y, dt) && total / 4 < (1UL << 30) && (size_t)n * h * w * c / 4 < (1UL << 30)) {
+        CN_DISPATCH_DT(dt, hipLaunchKernelGGL((maxpool_fwd4_kernel<T>), dim3(ew_blocks(total / 4)), dim3(256), 0, (hipStream_t)stream,
+                                              (const T*)x, (T*)y, n, h, w, c / 4, oh, ow, k, s, pad));
+        CN_LAUNCH_CHECK();
+        return CN_OK;
+    }
     CN_DISPATCH_DT(dt, hipLaunchKernelGGL((maxpool_fwd_kernel<T>), dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, n, h, w, c, oh, ow, k, s, pad));
     CN_LAUNCH_CHECK();
     return CN_OK;

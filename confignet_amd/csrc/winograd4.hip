@@ -96,8 +96,23 @@ constexpr int W4_RAW = W4_RAW_PIECES * 256;
 constexpr int W4_BUF = 2 * W4_U + 2 * W4_RAW;     // floats: 116.7 KB (the epilogue's exchange buffer needs 96 KB of it)
 
 
+// Epilogue modes (cn_conv_fwd_wino4_ep): what the column pass of the output transform does with the finished pixels it holds in
+// registers besides storing them.  W4_EP_NONE is cn_conv_fwd_wino4's launch.
+//   POOL       also stores the 2 x 2 / stride-2 maximum of the activated output to P (n, h / 2, w / 2, cout): a 4 x 4 tile holds whole
+//              windows.  A thread owns a column PAIR of its tile (4 rows x 2 columns x 4 channels) instead of one column.
+//   POOL_ONLY  as POOL, the full-size output is not stored (Y is not touched).
+//   MASK       data gradient:  Y = (r [+ (y - t) s[sample] k]) relu'(y),  r the transformed result, y (and the target t, if given) loaded
+//              at the store address -- the elementwise step of the layer in front (cn_act_bwd / cn_tap_bwd), same operand order.
+enum { W4_EP_NONE = 0, W4_EP_POOL = 1, W4_EP_POOL_ONLY = 2, W4_EP_MASK = 3 };
+template <int EP> struct Wino4Ep {};
+template <> struct Wino4Ep<W4_EP_POOL> { float* P; };
+template <> struct Wino4Ep<W4_EP_POOL_ONLY> { float* P; };
+template <> struct Wino4Ep<W4_EP_MASK> { const float* Ym; const float* T; const float* S; int s_rows; float k; };
+
+template <int EP>
 __global__ __launch_bounds__(768) void wino4_fwd_kernel(Wino4Geom g, const float* __restrict__ X, const float* __restrict__ U,
-                                                        const float* __restrict__ bias, float* __restrict__ Y, int act, float slope) {
+                                                        const float* __restrict__ bias, float* __restrict__ Y, int act, float slope,
+                                                        Wino4Ep<EP> ep) {
     __shared__ __attribute__((aligned(16))) float Vs[2][36][W4_KC][W4_VP];      // V planes, k-major: [stage][position][k][tile]
     extern __shared__ __attribute__((aligned(16))) float BUF[];                 // U0 | U1 | RAW0 | RAW1 (DMA destinations)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -324,7 +339,10 @@ __global__ __launch_bounds__(768) void wino4_fwd_kernel(Wino4Geom g, const float
             }
         }
         __syncthreads();
+        if constexpr (EP == W4_EP_NONE) {
         // column pass: a thread owns 4 consecutive channels of one (tile, y): 16-byte LDS reads and 16-byte stores
+        // (this branch is the kernel as it was before the epilogue modes, statement for statement: the instance compiles to the same
+        // instructions; the modes below share the arithmetic through `column`)
         for (int idx = tid; idx < 1024; idx += 768) {
             const int c4 = idx & 7, tl = (idx >> 3) & 31, y = idx >> 8;
             float4 m[6];
@@ -347,6 +365,79 @@ __global__ __launch_bounds__(768) void wino4_fwd_kernel(Wino4Geom g, const float
             *reinterpret_cast<float4*>(dst + 2 * rs) = make_float4(cn_apply_act(o2x, act, slope), cn_apply_act(o2y, act, slope), cn_apply_act(o2z, act, slope), cn_apply_act(o2w, act, slope));
             *reinterpret_cast<float4*>(dst + 3 * rs) = make_float4(cn_apply_act(o3x, act, slope), cn_apply_act(o3y, act, slope), cn_apply_act(o3z, act, slope), cn_apply_act(o3w, act, slope));
         }
+        } else {
+        auto column = [&](int c4, int tl, int y, float4 (&o)[4]) {      // the 4 rows of column y of tile tl, bias and activation applied
+            float4 m[6];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) m[i] = *reinterpret_cast<const float4*>(E + ((i * 4 + y) * 32 + tl) * 32 + 4 * c4);
+            const int co = co0 + rb * 32 + 4 * c4;
+            const float4 bv = bias ? *reinterpret_cast<const float4*>(bias + co) : make_float4(0.f, 0.f, 0.f, 0.f);
+#define W4_O(f)                                                                                                          \
+            const float s12##f = m[1].f + m[2].f, d12##f = m[1].f - m[2].f, s34##f = m[3].f + m[4].f, d34##f = m[3].f - m[4].f; \
+            const float o0##f = m[0].f + s12##f + s34##f + bv.f, o1##f = d12##f + 2.f * d34##f + bv.f,                     \
+                        o2##f = s12##f + 4.f * s34##f + bv.f, o3##f = d12##f + 8.f * d34##f + m[5].f + bv.f;
+            W4_O(x) W4_O(y) W4_O(z) W4_O(w)
+#undef W4_O
+            o[0] = make_float4(cn_apply_act(o0x, act, slope), cn_apply_act(o0y, act, slope), cn_apply_act(o0z, act, slope), cn_apply_act(o0w, act, slope));
+            o[1] = make_float4(cn_apply_act(o1x, act, slope), cn_apply_act(o1y, act, slope), cn_apply_act(o1z, act, slope), cn_apply_act(o1w, act, slope));
+            o[2] = make_float4(cn_apply_act(o2x, act, slope), cn_apply_act(o2y, act, slope), cn_apply_act(o2z, act, slope), cn_apply_act(o2w, act, slope));
+            o[3] = make_float4(cn_apply_act(o3x, act, slope), cn_apply_act(o3y, act, slope), cn_apply_act(o3z, act, slope), cn_apply_act(o3w, act, slope));
+        };
+        const long rs = (long)g.w * g.cout;
+        if constexpr (EP == W4_EP_POOL || EP == W4_EP_POOL_ONLY) {
+            // a thread owns a column PAIR of one tile: 32 tiles x 2 pairs x 8 channel groups = 512 items of 4 rows x 2 columns x 4
+            // channels = two whole windows per channel, their maxima taken from the registers
+            if (tid < 512) {
+                const int c4 = tid & 7, tl = (tid >> 3) & 31, yp = tid >> 8;
+                const int co = co0 + rb * 32 + 4 * c4;
+                const int otx = (tl & 3) + 4 * ((tl >> 3) & 1), oty = ((tl >> 2) & 1) + 2 * (tl >> 4);
+                const int row0 = by * 16 + 4 * oty, col = bx * 32 + 4 * otx + 2 * yp;
+                float4 o[2][4];
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    column(c4, tl, 2 * yp + q, o[q]);
+                    if constexpr (EP == W4_EP_POOL) {
+                        float* dst = Y + ((long)(img * g.h + row0) * g.w + col + q) * g.cout + co;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) *reinterpret_cast<float4*>(dst + r * rs) = o[q][r];
+                    }
+                }
+                const int ph = g.h >> 1, pw = g.w >> 1;
+                float* pdst = ep.P + ((long)(img * ph + (row0 >> 1)) * pw + (col >> 1)) * g.cout + co;
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {                       // (the scan order and fmaxf chain of maxpool_fwd_kernel)
+#define W4_MAX(f) fmaxf(fmaxf(fmaxf(fmaxf(-INFINITY, o[0][2 * r].f), o[1][2 * r].f), o[0][2 * r + 1].f), o[1][2 * r + 1].f)
+                    *reinterpret_cast<float4*>(pdst + r * (long)pw * g.cout) = make_float4(W4_MAX(x), W4_MAX(y), W4_MAX(z), W4_MAX(w));
+#undef W4_MAX
+                }
+            }
+        } else {
+            // MASK: the default ownership (4 rows of one column); y and the target are read at the store address
+            for (int idx = tid; idx < 1024; idx += 768) {
+                const int c4 = idx & 7, tl = (idx >> 3) & 31, y = idx >> 8;
+                float4 o[4];
+                column(c4, tl, y, o);
+                const int co = co0 + rb * 32 + 4 * c4;
+                const int otx = (tl & 3) + 4 * ((tl >> 3) & 1), oty = ((tl >> 2) & 1) + 2 * (tl >> 4);
+                const int row0 = by * 16 + 4 * oty, col = bx * 32 + 4 * otx + y;
+                const long off = ((long)(img * g.h + row0) * g.w + col) * g.cout + co;
+                const float f = ep.T ? ep.S[ep.s_rows == 1 ? 0 : img] * ep.k : 0.f;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float4 u = *reinterpret_cast<const float4*>(ep.Ym + off + r * rs);
+                    float4 v = o[r];
+                    if (ep.T) {                                     // cn_tap_bwd's order: difference times factor, plus gradient, times derivative
+                        const float4 t = *reinterpret_cast<const float4*>(ep.T + off + r * rs);
+                        float4 d = make_float4((u.x - t.x) * f, (u.y - t.y) * f, (u.z - t.z) * f, (u.w - t.w) * f);
+                        d.x += v.x; d.y += v.y; d.z += v.z; d.w += v.w;
+                        v = d;
+                    }
+                    *reinterpret_cast<float4*>(Y + off + r * rs) = make_float4(v.x * act_deriv(u.x, CN_ACT_RELU, 0.f), v.y * act_deriv(u.y, CN_ACT_RELU, 0.f),
+                                                                               v.z * act_deriv(u.z, CN_ACT_RELU, 0.f), v.w * act_deriv(u.w, CN_ACT_RELU, 0.f));
+                }
+            }
+        }
+        }
         __syncthreads();
     }
 }
@@ -362,6 +453,26 @@ extern "C" int cn_conv_wino4_filter(const float* w, float* u, int cin, int cout,
     return CN_OK;
 }
 
+// One launch of instance EP; bytes: what the launch moves through memory (operands, filter, outputs).
+template <int EP>
+static int wino4_launch(int n, int h, int w, int cin, int cout, const float* x, const float* u, const float* bias, float* y, int act,
+                        float slope, Wino4Ep<EP> ep, double bytes, hipStream_t s) {
+    Wino4Geom g{n, h, w, cin, cout, h / 16, w / 32};
+    const long nblk = (long)n * g.bh * g.bw;
+    constexpr size_t lds = sizeof(float) * W4_BUF;           // + 36 KB static (V planes)
+    static bool attr_set = false;
+    if (!attr_set) {
+        CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(wino4_fwd_kernel<EP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        attr_set = true;
+    }
+    // MFMA work that contributes to the result: 36 products per 4x4 output tile and (ci, co) pair
+    cn_prof_begin(s, 2.0 * 36.0 * (double)nblk * W4_T * cin * cout, bytes, CN_FAM_WINO);
+    hipLaunchKernelGGL((wino4_fwd_kernel<EP>), dim3((unsigned)(nblk * (cout / W4_C))), dim3(768), lds, s, g, x, u, bias, y, act, slope, ep);
+    cn_prof_end(s);
+    CN_LAUNCH_CHECK();
+    return CN_OK;
+}
+
 // x (n, h, w, cin) -> y (n, h, w, cout): 3x3, stride 1, SAME; u from cn_conv_wino4_filter ([36][cin][cout]).
 // Returns CN_EUNSUPPORTED (nothing launched) unless h % 16 == 0, w % 32 == 0, cin % 16 == 0 and cout % 64 == 0.
 extern "C" int cn_conv_fwd_wino4(int n, int h, int w, int cin, int cout, const float* x, const float* u, const float* bias,
@@ -370,19 +481,37 @@ extern "C" int cn_conv_fwd_wino4(int n, int h, int w, int cin, int cout, const f
     if (h % 16 || w % 32 || cin % 16 || cout % W4_C) return CN_EUNSUPPORTED;
     CN_CHECK_ARG((double)n * h * w * (cin > cout ? cin : cout) * 4.0 < 2147483647.0 && 144.0 * cin * cout < 2147483647.0,
                  "tensor exceeds 2^31 bytes (buffer descriptors, 32-bit offsets)");
-    Wino4Geom g{n, h, w, cin, cout, h / 16, w / 32};
-    const long nblk = (long)n * g.bh * g.bw;
-    constexpr size_t lds = sizeof(float) * W4_BUF;           // + 36 KB static (V planes)
-    static bool attr_set = false;
-    if (!attr_set) {
-        CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(wino4_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
+    return wino4_launch<W4_EP_NONE>(n, h, w, cin, cout, x, u, bias, y, act, slope, Wino4Ep<W4_EP_NONE>{},
+                                    4.0 * ((double)n * h * w * (cin + cout) + 36.0 * cin * cout), (hipStream_t)stream);
+}
+
+// The same launch with an epilogue mode (CN_W4_EP_*): POOL (y and pooled), POOL_ONLY (pooled; y is not touched and may be NULL), MASK (ym =
+// the ReLU output whose derivative masks the result; target / s / k: the tap term, s_rows = 1 or n scales; target NULL: none).
+// Same geometry limits; anything else it does not take: CN_EUNSUPPORTED, nothing launched.
+extern "C" int cn_conv_fwd_wino4_ep(int n, int h, int w, int cin, int cout, const float* x, const float* u, const float* bias, float* y,
+                                    int act, float slope, int mode, float* pooled, const float* ym, const float* target, const float* s,
+                                    int s_rows, float k, void* stream) {
+    CN_CHECK_ARG(x && u && n > 0 && h > 0 && w > 0, "conv_fwd_wino4_ep: bad args");
+    if (h % 16 || w % 32 || cin % 16 || cout % W4_C) return CN_EUNSUPPORTED;
+    if (mode != CN_W4_EP_POOL && mode != CN_W4_EP_POOL_ONLY && mode != CN_W4_EP_MASK) return CN_EUNSUPPORTED;
+    const auto al16 = [](const void* p) { return ((size_t)p & 15) == 0; };
+    if (mode == CN_W4_EP_MASK) {
+        CN_CHECK_ARG(y && ym && (!target || (s && (s_rows == 1 || s_rows == n))), "conv_fwd_wino4_ep: MASK needs y, ym and, with a target, 1 or n scales");
+        if (!al16(y) || !al16(ym) || !al16(target)) return CN_EUNSUPPORTED;
+    } else {
+        CN_CHECK_ARG(pooled && (y || mode == CN_W4_EP_POOL_ONLY), "conv_fwd_wino4_ep: POOL needs y and pooled");
+        if (!al16(pooled) || !al16(y)) return CN_EUNSUPPORTED;
     }
-    hipStream_t s = (hipStream_t)stream;
-    // MFMA work that contributes to the result: 36 products per 4x4 output tile and (ci, co) pair
-    cn_prof_begin(s, 2.0 * 36.0 * (double)nblk * W4_T * cin * cout, 4.0 * ((double)n * h * w * (cin + cout) + 36.0 * cin * cout), CN_FAM_WINO);
-    hipLaunchKernelGGL(wino4_fwd_kernel, dim3((unsigned)(nblk * (cout / W4_C))), dim3(768), lds, s, g, x, u, bias, y, act, slope);
-    cn_prof_end(s);
-    CN_LAUNCH_CHECK();
-    return CN_OK;
+    CN_CHECK_ARG((double)n * h * w * (cin > cout ? cin : cout) * 4.0 < 2147483647.0 && 144.0 * cin * cout < 2147483647.0,
+                 "tensor exceeds 2^31 bytes (buffer descriptors, 32-bit offsets)");
+    const double px = (double)n * h * w, flt = 36.0 * cin * cout;
+    hipStream_t st = (hipStream_t)stream;
+    if (mode == CN_W4_EP_POOL)
+        return wino4_launch<W4_EP_POOL>(n, h, w, cin, cout, x, u, bias, y, act, slope, Wino4Ep<W4_EP_POOL>{pooled},
+                                        4.0 * (px * (cin + 1.25 * cout) + flt), st);
+    if (mode == CN_W4_EP_POOL_ONLY)
+        return wino4_launch<W4_EP_POOL_ONLY>(n, h, w, cin, cout, x, u, bias, y, act, slope, Wino4Ep<W4_EP_POOL_ONLY>{pooled},
+                                             4.0 * (px * (cin + 0.25 * cout) + flt), st);
+    return wino4_launch<W4_EP_MASK>(n, h, w, cin, cout, x, u, bias, y, act, slope, Wino4Ep<W4_EP_MASK>{ym, target, s, s_rows, k},
+                                    4.0 * (px * (cin + (target ? 3.0 : 2.0) * cout) + flt), st);
 }

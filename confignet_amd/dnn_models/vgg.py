@@ -14,6 +14,20 @@ VGG16_CFG = [64, 64, "P", 128, 128, "P", 256, 256, 256, "P", 512, 512]
 VGG19_TAPS = (0, 1, 5, 9)    # conv ordinals of keras layers[1, 2, 8, 13]
 VGG16_TAPS = (0, 1, 5, 8)    # conv ordinals of keras layers[1, 2, 8, 12]
 C3 = ConvSpec((3, 3))
+# The pools, and in the backward walk the ReLU masks and tap terms, taken in the epilogues of the F(4x4) launches next to them
+# (ops.conv_fwd_pool / ops.conv_dgrad_masked) where those launches exist; False: every one of them is a pass of its own (A/B, tests).
+VGG_FUSED_EPILOGUES = True
+
+
+def _pool_follows(cfg):
+    """Conv ordinals of cfg that are followed by a pool."""
+    out, ci = set(), 0
+    for i, item in enumerate(cfg):
+        if item != "P":
+            if i + 1 < len(cfg) and cfg[i + 1] == "P":
+                out.add(ci)
+            ci += 1
+    return out
 
 
 class VGGFeatures(Net):
@@ -29,12 +43,23 @@ class VGGFeatures(Net):
         self.finalize()
 
     def __call__(self, x_pre):
+        from .. import ops
         feats, ci, x = [], 0, x_pre
-        for item in self.cfg:
+        # without a tape a convolution in front of a pool writes the pooled tensor itself, and its full-size output only at a tap
+        fuse = VGG_FUSED_EPILOGUES and not torch.is_grad_enabled()
+        pooled = None
+        for i, item in enumerate(self.cfg):
             if item == "P":
-                x = F.maxpool(x, 2, 2)
+                x, pooled = (F.maxpool(x, 2, 2) if pooled is None else pooled), None
             else:
-                x = F.conv(x, self.weights[2 * ci], self.weights[2 * ci + 1], C3, ACT_RELU)
+                w, b = self.weights[2 * ci], self.weights[2 * ci + 1]
+                r = None
+                if fuse and i + 1 < len(self.cfg) and self.cfg[i + 1] == "P":
+                    r = ops.conv_fwd_pool(x.contiguous(), w, b, C3.geom(tuple(x.shape), w.shape[-1]), ACT_RELU, 0.0, keep_full=ci in self.taps)
+                if r is not None:
+                    x, pooled = r
+                else:
+                    x = F.conv(x, w, b, C3, ACT_RELU)
                 if ci in self.taps:
                     feats.append(x)
                 ci += 1
@@ -48,19 +73,30 @@ class VGGLossFn(torch.autograd.Function):
     (cn_tap_bwd) instead of the loss term's gradient pass, autograd's add of the two gradients and the ReLU backward (9 -> 4
     tensor passes on the 134 MB taps of the benchmark's size).  `sizes` = None: one scalar over the whole batch; else the
     consecutive sample groups of PerceptualLoss.loss_groups, one scalar each.  Gradient w.r.t. x only (the stack is frozen).
-    First-order only.  Inputs: net, x (preprocessed image), sizes, then the targets of the taps."""
+    First-order only.  Inputs: net, x (preprocessed image), sizes, then the targets of the taps.
+    Where the launch next to it is Winograd F(4x4) (VGG_FUSED_EPILOGUES), a pool is taken in the epilogue of the convolution in front
+    of it, and a layer's elementwise backward step in the epilogue of the data gradient that produces its incoming gradient."""
 
     @staticmethod
     def forward(ctx, net, x, sizes, *targets):
         from .. import ops
         x = x.contiguous()
         ys, feats, ci, t = [], [], 0, x
-        for item in net.cfg:
+        pooled = None
+        for i, item in enumerate(net.cfg):
             if item == "P":
-                t = ops.maxpool_fwd(t, 2, 2, 0)           # (its input is the previous convolution's output: ys[ci - 1])
+                # (its input is the previous convolution's output, ys[ci - 1]; that launch's epilogue has pooled it where it could)
+                t, pooled = (ops.maxpool_fwd(t, 2, 2, 0) if pooled is None else pooled), None
             else:
                 w, b = net.weights[2 * ci], net.weights[2 * ci + 1]
-                t = ops.conv_fwd(t, w, b, C3.geom(tuple(t.shape), w.shape[-1]), ACT_RELU)
+                geom = C3.geom(tuple(t.shape), w.shape[-1])
+                r = None
+                if VGG_FUSED_EPILOGUES and i + 1 < len(net.cfg) and net.cfg[i + 1] == "P":
+                    r = ops.conv_fwd_pool(t, w, b, geom, ACT_RELU)          # (the backward pass needs the full-size output)
+                if r is not None:
+                    t, pooled = r
+                else:
+                    t = ops.conv_fwd(t, w, b, geom, ACT_RELU)
                 ys.append(t)
                 if ci in net.taps:
                     feats.append(t)
@@ -93,39 +129,58 @@ class VGGLossFn(torch.autograd.Function):
         n = x.shape[0]
         g = g.reshape(-1).float()
         tap_of = {ci: k for k, ci in enumerate(net.taps)}
-        gcur, ci, pooled = None, ny, None
+        before_pool, last_tap = _pool_follows(net.cfg), max(net.taps)
+
+        def tap_scale(ci):
+            per = ys[ci].numel() // n
+            if sizes is None:
+                return g.contiguous(), 2.0 / (n * per)               # one row = the whole tensor
+            return torch.cat([g[i:i + 1].expand(sz) * (1.0 / (sz * per)) for i, sz in enumerate(sizes)]).contiguous(), 2.0
+
+        gcur, ci, pooled, stepped = None, ny, None, False
         for item in reversed(net.cfg):
             if item == "P":
                 pooled, gcur = gcur, None             # the pool's backward joins the ReLU backward of the layer in front of it
                 continue
             ci -= 1
             y = ys[ci]
-            s_ = k = None
-            if ci in tap_of:
-                per = y.numel() // n
-                if sizes is None:
-                    s_, k = g.contiguous(), 2.0 / (n * per)          # one row = the whole tensor
-                else:
-                    s_ = torch.cat([g[i:i + 1].expand(sz) * (1.0 / (sz * per)) for i, sz in enumerate(sizes)]).contiguous()
-                    k = 2.0
-            gu = None
-            if pooled is not None:
-                # ReLU -> MaxPooling2D backward in ONE pass (the tap's own term added there too): no full-size gradient in between
-                gu = ops.maxpool2_bwd_relu(y, pooled, targets[tap_of[ci]] if s_ is not None else None, s_, k if s_ is not None else 0.0)
-                if gu is None:
-                    gcur = ops.maxpool_bwd(y, pooled, 2, 2, 0)
-                pooled = None
-            if gu is not None:
-                pass
-            elif s_ is not None:
-                gu = ops.tap_bwd(y, targets[tap_of[ci]], gcur, s_, k, ACT_RELU)
-            elif gcur is None:
-                continue                                             # (layers behind the last tap carry no gradient)
+            if stepped:
+                # this layer's elementwise step was taken in the epilogue of the data gradient that produced gcur
+                gu, stepped = gcur, False
             else:
-                gu = ops.act_bwd(gcur, y, ACT_RELU)
+                s_ = k = None
+                if ci in tap_of:
+                    s_, k = tap_scale(ci)
+                gu = None
+                if pooled is not None:
+                    # ReLU -> MaxPooling2D backward in ONE pass (the tap's own term added there too): no full-size gradient in between
+                    gu = ops.maxpool2_bwd_relu(y, pooled, targets[tap_of[ci]] if s_ is not None else None, s_, k if s_ is not None else 0.0)
+                    if gu is None:
+                        gcur = ops.maxpool_bwd(y, pooled, 2, 2, 0)
+                    pooled = None
+                if gu is not None:
+                    pass
+                elif s_ is not None:
+                    gu = ops.tap_bwd(y, targets[tap_of[ci]], gcur, s_, k, ACT_RELU)
+                elif gcur is None:
+                    continue                                             # (layers behind the last tap carry no gradient)
+                else:
+                    gu = ops.act_bwd(gcur, y, ACT_RELU)
             w = net.weights[2 * ci]
             in_shape = conv_input_shape(net.cfg, ci, ctx.x_shape)
-            gcur = ops.conv_dgrad(gu, w, C3.geom(in_shape, w.shape[-1]))
+            geom = C3.geom(in_shape, w.shape[-1])
+            gcur = None
+            if VGG_FUSED_EPILOGUES and ci >= 1 and ci - 1 not in before_pool and ci - 1 != last_tap:
+                # the elementwise step of the layer in front (ReLU mask, and the tap term at a tap) in this launch's epilogue
+                yp = ys[ci - 1]
+                if ci - 1 in tap_of:
+                    sp, kp = tap_scale(ci - 1)
+                    gcur = ops.conv_dgrad_masked(gu, w, geom, yp, targets[tap_of[ci - 1]], sp, kp)
+                else:
+                    gcur = ops.conv_dgrad_masked(gu, w, geom, yp)
+                stepped = gcur is not None
+            if gcur is None:
+                gcur = ops.conv_dgrad(gu, w, geom)
         return None, gcur, None, *([None] * len(targets))
 
 

@@ -441,6 +441,44 @@ def conv_fwd(x, w, bias, g, act=ACT_NONE, slope=0.0):
     return cast(y, out_dtype)
 
 
+W4_EP_POOL, W4_EP_POOL_ONLY, W4_EP_MASK = 1, 2, 3        # epilogue modes of cn_conv_fwd_wino4_ep (include/confignet_hip.h)
+
+
+def conv_fwd_pool(x, w, bias, g, act=ACT_NONE, slope=0.0, keep_full=True):
+    """(y or None, maxpool 2x2/2 of y) for y = act(conv(x, w) + bias), the pool taken in the F(4x4) launch's epilogue
+    (cn_conv_fwd_wino4_ep); keep_full=False: y is neither stored nor returned.  None where the layer is not an fp32 F(4x4)
+    launch: the caller then runs conv_fwd and maxpool_fwd."""
+    if not (ACT_DTYPE == torch.float32 and x.dtype == torch.float32 and _wino4_ok(g, g.cin, g.cout)):
+        return None
+    _stats.request = _stats.ready = None                 # (as conv_fwd: a request applies to the next convolution only)
+    y = torch.empty(geom_out_shape(g), device=x.device, dtype=torch.float32) if keep_full else None
+    pooled = torch.empty((g.n, g.in_h // 2, g.in_w // 2, g.cout), device=x.device, dtype=torch.float32)
+    check(lib.cn_conv_fwd_wino4_ep(g.n, g.in_h, g.in_w, g.cin, g.cout, _ptr(_c(x)), _ptr(_wino4_filter(w, False)), _fptr(bias), _ptr(y),
+                                   act, slope, W4_EP_POOL if keep_full else W4_EP_POOL_ONLY, _ptr(pooled), None, None, None, 1, 0.0,
+                                   _stream()), "cn_conv_fwd_wino4_ep")
+    prof_note_saved(wino4_saved_flops(g))
+    return y, pooled
+
+
+def conv_dgrad_masked(gy, w, g, y, target=None, s=None, k=0.0):
+    """(conv_dgrad(gy, w, g) [+ (y - target) s[sample] k]) relu'(y): the data gradient of the convolution described by g with the
+    elementwise backward step of the layer in front (act_bwd, or tap_bwd at a tapped layer; y = that layer's ReLU output, the
+    shape of g's input) in the F(4x4) launch's epilogue.  s: 1 or n scales.  None where the data gradient is not an fp32 F(4x4)
+    launch: the caller then runs the two passes."""
+    if not (ACT_DTYPE == torch.float32 and gy.dtype == torch.float32 and y.dtype == torch.float32 and _wino4_ok(g, g.cout, g.cin)):
+        return None
+    if target is not None and (target.dtype != torch.float32 or s is None or s.numel() not in (1, g.n)):
+        return None
+    _log_mask(y, ACT_RELU)
+    gu = torch.empty(geom_in_shape(g, upsampled=True), device=gy.device, dtype=torch.float32)
+    check(lib.cn_conv_fwd_wino4_ep(g.n, g.in_h, g.in_w, g.cout, g.cin, _ptr(_c(gy)), _ptr(_wino4_filter(w, True)), None, _ptr(gu),
+                                   ACT_NONE, 0.0, W4_EP_MASK, None, _ptr(_c(y)), None if target is None else _ptr(_c(target)),
+                                   None if target is None else _fptr(s), 1 if target is None else s.numel(), k, _stream()),
+          "cn_conv_fwd_wino4_ep")
+    prof_note_saved(wino4_saved_flops(g))
+    return gu
+
+
 def conv_fwd_res(x, w, bias, res, g, act=ACT_NONE, slope=0.0):
     """act(conv(x, w) + bias + res): the residual add of a ResNet block in the convolution's epilogue where the launch carries it
     (cn_conv_fwd_res: unsplit implicit-GEMM launches), else convolution + one nc_lin2 pass."""

@@ -224,6 +224,19 @@ int cn_conv_fwd_wino(int n, int h, int w, int cin, int cout, const float* x, con
 int cn_conv_wino4_filter(const float* w, float* u, int cin, int cout, int dgrad, void* stream);
 int cn_conv_fwd_wino4(int n, int h, int w, int cin, int cout, const float* x, const float* u, const float* bias,
                       float* y, int act, float slope, void* stream);
+/* The F(4x4) launch with an epilogue mode: what the output transform does with the finished pixels besides storing them.
+ *   CN_W4_EP_POOL       also writes the 2x2 / stride-2 maximum of the activated output to pooled (n, h/2, w/2, cout) = cn_maxpool_fwd of y
+ *   CN_W4_EP_POOL_ONLY  as POOL, y is not written (and may be NULL)
+ *   CN_W4_EP_MASK       data gradient: y = (r [+ (ym - target) s[sample] k]) relu'(ym), r the convolution's result, ym the ReLU output of
+ *                       the layer whose input gradient this is; target NULL: no tap term; s_rows = 1 (one scale) or n: the result of
+ *                       cn_conv_fwd_wino4 followed by cn_act_bwd / cn_tap_bwd (up to the contraction of the tap term's multiply-add)
+ * Geometry limits of cn_conv_fwd_wino4, tensors 16-byte aligned; anything else: CN_EUNSUPPORTED, nothing launched. */
+#define CN_W4_EP_POOL 1
+#define CN_W4_EP_POOL_ONLY 2
+#define CN_W4_EP_MASK 3
+int cn_conv_fwd_wino4_ep(int n, int h, int w, int cin, int cout, const float* x, const float* u, const float* bias, float* y,
+                         int act, float slope, int mode, float* pooled, const float* ym, const float* target, const float* s,
+                         int s_rows, float k, void* stream);
 /* Tuning hook: force the tile configuration (0 = 128x128, 1 = 128x64, 2 = 64x64, 3 = 128x32, 4 = 128x96; -1 = heuristic), the
  * split-K factor of cn_conv_fwd / cn_conv_dgrad (0 = heuristic) and the workgroup target of cn_conv_wgrad (0 = default). */
 int cn_conv_tune(int cfg, int splits, long wg_blocks);
