@@ -139,6 +139,14 @@ SIGNATURES = {
     "cn_avgpool3_same": [_p, _p, _i, _i, _i, _i, _i, _p],
     "cn_dwconv3x3_fwd": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p],
     "cn_image_preprocess": [_p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _f, _p],
+    "cn_dwconv3x3_dgrad": [_p, _p, _p, _i, _i, _i, _i, _i, _p],
+    "cn_dwconv3x3_wgrad_slices": [_i, _i, _i, _i, _i],
+    "cn_dwconv3x3_wgrad": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
+    "cn_bn_train_coef": [_p] * 12 + [ctypes.c_longlong, _i, _f, ctypes.c_double, _i, _p],
+    "cn_bn_train_apply": [_p, _p, _p, _p, ctypes.c_longlong, _i, _i, _p],
+    "cn_bn_train_bwd_slices": [ctypes.c_longlong, _i],
+    "cn_bn_train_bwd_reduce": [_p] * 6 + [_i, ctypes.c_longlong, _i, _i, _p],
+    "cn_bn_train_bwd_apply": [_p] * 8 + [ctypes.c_longlong, _i, _i, _p],
     "cn_chan_affine3_fwd": [_p, _p, _z, ctypes.POINTER(_i), _f, ctypes.POINTER(_f), _p],
     "cn_chan_affine3_bwd": [_p, _p, _z, ctypes.POINTER(_i), _f, _p],
     "cn_gan_loss_fwd": [_p, _p, _i, _f, _p],

@@ -1368,6 +1368,91 @@ def dwconv3x3_fwd(x, w, bias, stride, act=ACT_NONE, slope=0.0):
     return y
 
 
+def dwconv3x3_dgrad(gy, w, in_shape, stride, out=None):
+    """Input gradient of dwconv3x3_fwd (no bias, no activation): gy (n, ceil(h / stride), ceil(w / stride), c) -> gx
+    in_shape = (n, h, w, c) (cn_dwconv3x3_dgrad, a gather).  out: write into this contiguous tensor."""
+    gy = _c(f32(gy))
+    n, h, wd, c = (int(v) for v in in_shape)
+    assert tuple(gy.shape) == (n, -(-h // stride), -(-wd // stride), c), (tuple(gy.shape), tuple(in_shape), stride)
+    assert tuple(w.shape) in ((3, 3, c, 1), (3, 3, c))
+    gx = out if out is not None else torch.empty((n, h, wd, c), device=gy.device, dtype=torch.float32)
+    assert gx.is_contiguous() and gx.numel() == n * h * wd * c
+    check(lib.cn_dwconv3x3_dgrad(_ptr(gy), _fptr(_c(w)), _fptr(gx), n, h, wd, c, stride, _stream()), "cn_dwconv3x3_dgrad")
+    return gx
+
+
+def dwconv3x3_wgrad(x, gy, stride, out=None, accumulate=True, defer=True):
+    """Filter gradient (3, 3, c, 1) of dwconv3x3_fwd.  cn_dwconv3x3_wgrad leaves one partial filter per slice of output pixels
+    (the library's plan: cn_dwconv3x3_wgrad_slices) and sum_rows_into adds the slices in slice order -- as every per-channel
+    reduction with partial rows here, with no atomics, so the default and the deterministic mode give the same bits.
+    out: ADD the gradient to this tensor (a slot of a gradient arena); out with accumulate=False: WRITE it there.  Inside a
+    grad_sink an accumulating sum joins the pass' grouped reduction unless defer=False (as conv_wgrad)."""
+    x, gy = _c(f32(x)), _c(f32(gy))
+    n, h, wd, c = x.shape
+    assert tuple(gy.shape) == (n, -(-h // stride), -(-wd // stride), c), (tuple(gy.shape), tuple(x.shape), stride)
+    slices = lib.cn_dwconv3x3_wgrad_slices(n, h, wd, c, stride)
+    if slices <= 0:
+        check(slices, "cn_dwconv3x3_wgrad_slices")
+    part = torch.empty((slices, 9 * c), device=x.device, dtype=torch.float32)
+    check(lib.cn_dwconv3x3_wgrad(_ptr(x), _ptr(gy), _fptr(part), slices, n, h, wd, c, stride, _stream()), "cn_dwconv3x3_wgrad")
+    if out is None:
+        out, accumulate = torch.empty((3, 3, c, 1), device=x.device, dtype=torch.float32), False
+    assert out.is_contiguous() and out.numel() == 9 * c and out.dtype == torch.float32
+    sum_rows_into(part, out.view(-1), accumulate=accumulate, defer=defer)
+    return out
+
+
+def sink_dwconv3x3_wgrad(x, gy, stride, slot):
+    """The depthwise filter gradient ADDED into its gradient-arena slot (a leaf of the backward pass, as sink_conv_wgrad)."""
+    dwconv3x3_wgrad(x, gy, stride, out=slot)
+
+
+BN_MOMENTUM = 0.99
+
+
+def bn_train_fwd(x, gamma, beta, moving_mean=None, moving_var=None, act=ACT_NONE, eps=1e-3, momentum=BN_MOMENTUM, bessel=True):
+    """Training-mode BatchNormalization over every axis but the last, then `act` (ACT_NONE / ACT_RELU6): one reduce pass
+    (nc_reduce per channel), the coefficients (cn_bn_train_coef: a = gamma rsqrt(var + eps), b = beta - mean a; it also
+    updates the moving statistics IN PLACE, the variance Bessel-corrected if `bessel`), one apply pass y = act(a x + b).
+    Returns (y, saved) with saved = (mean, var, r, a) per channel for bn_train_bwd (var: the biased batch variance)."""
+    x = _c(f32(x))
+    c = x.shape[-1]
+    m = x.numel() // c
+    s1, s2 = nc_reduce(x, None, per_channel=True)
+    co = torch.empty((5, c), device=x.device, dtype=torch.float32)                 # mean | var | r | a | b
+    check(lib.cn_bn_train_coef(_fptr(_c(s1)), _fptr(_c(s2)), _fptr(_c(gamma)), _fptr(_c(beta)), _fptr(x), _fptr(co[0]), _fptr(co[1]),
+                               _fptr(co[2]), _fptr(co[3]), _fptr(co[4]), _fptr(moving_mean), _fptr(moving_var), m, c, eps, momentum,
+                               int(bool(bessel)), _stream()), "cn_bn_train_coef")
+    y = torch.empty_like(x)
+    check(lib.cn_bn_train_apply(_fptr(x), _fptr(co[3]), _fptr(co[4]), _fptr(y), m, c, act, _stream()), "cn_bn_train_apply")
+    return y, (co[0], co[1], co[2], co[3])
+
+
+def bn_train_bwd(gy, y, x, saved, act=ACT_NONE):
+    """(gx, dgamma, dbeta) of bn_train_fwd: g = gy 1[0 < y < 6] (ACT_RELU6; y may be None for ACT_NONE), dbeta = sum g,
+    dgamma = sum g xh in one reduce pass (cn_bn_train_bwd_reduce, per-slice partials added in slice order), then
+    gx = a (g - (dbeta + xh dgamma) / m) in one apply pass (cn_bn_train_bwd_apply)."""
+    mean, _, r, a = saved
+    gy, x = _c(f32(gy)), _c(f32(x))
+    c = x.shape[-1]
+    m = x.numel() // c
+    if BRANCH_LOG is not None and act == ACT_RELU6:
+        BRANCH_LOG.append(("relu6", ((y.detach() > 0) & (y.detach() < 6)).reshape(-1).cpu()))
+    slices = lib.cn_bn_train_bwd_slices(m, c)
+    if slices <= 0:
+        check(slices, "cn_bn_train_bwd_slices")
+    part = torch.empty((slices, 2 * c), device=x.device, dtype=torch.float32)
+    yp = _fptr(y) if act == ACT_RELU6 else None
+    check(lib.cn_bn_train_bwd_reduce(_fptr(gy), yp, _fptr(x), _fptr(mean), _fptr(r), _fptr(part), slices, m, c, act, _stream()),
+          "cn_bn_train_bwd_reduce")
+    sums = torch.empty(2 * c, device=x.device, dtype=torch.float32)
+    check(lib.cn_sum_rows_into(_fptr(part), _fptr(sums), slices, 2 * c, 0, _stream()), "cn_sum_rows_into")
+    gx = torch.empty_like(x)
+    check(lib.cn_bn_train_bwd_apply(_fptr(gy), yp, _fptr(x), _fptr(mean), _fptr(r), _fptr(a), _fptr(sums), _fptr(gx), m, c, act,
+                                    _stream()), "cn_bn_train_bwd_apply")
+    return gx, sums[c:], sums[:c]
+
+
 def image_preprocess(imgs, out_hw, from_signed=False):
     """A batch of images (n, h, w, c), uint8 or float32 in pixel units [0, 255], -> the MobileNetV2 input (n, out_h, out_w, c)
     fp32 in one launch: bilinear resampling with half-pixel centres and edge clamping (cv2.resize INTER_LINEAR) when the size

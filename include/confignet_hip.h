@@ -486,6 +486,39 @@ int cn_dwconv3x3_fwd(const float* x, const float* w, const float* bias, float* y
  * celeba_attribute_prediction.py:129-139 (the cv2.resize loop and preprocess_input of predict_attributes). */
 int cn_image_preprocess(const void* x, int x_dt, float* y, int n, int h, int wd, int c, int oh, int ow, float in_mul, float in_add,
                         void* stream);
+/* ---- training the attribute classifier (train_attribute_classifier.py, CelebaAttributeClassifier.train) --------------------
+ * Input gradient of cn_dwconv3x3_fwd (no bias, no activation): gx (n, h, wd, c), overwritten, from gy (n, ceil(h/s), ceil(wd/s), c):
+ * gx[b,iy,ix,ch] = sum_{ky,kx} gy[b,oy,ox,ch] w[ky,kx,ch] over the (oy, ox) with oy s - ph + ky = iy, ox s - pw + kx = ix.  A gather
+ * over gy: no atomics. */
+int cn_dwconv3x3_dgrad(const float* gy, const float* w, float* gx, int n, int h, int wd, int c, int stride, void* stream);
+/* Filter gradient of cn_dwconv3x3_fwd as per-slice partials: part (slices, 9 c), overwritten with plain stores,
+ * part[s][ky,kx,ch] = sum over the output pixels (b, oy, ox) of slice s of gy[b,oy,ox,ch] x[b, oy s - ph + ky, ox s - pw + kx, ch];
+ * the caller adds the slices in slice order (cn_sum_rows_into / cn_sum_parts_grouped with rows = slices, cols = 9 c): a fixed
+ * order and no atomics in every mode.  slices must be what cn_dwconv3x3_wgrad_slices returns for the same extents (a positive
+ * count; it needs no device). */
+int cn_dwconv3x3_wgrad_slices(int n, int h, int wd, int c, int stride);
+int cn_dwconv3x3_wgrad(const float* x, const float* gy, float* part, int slices, int n, int h, int wd, int c, int stride, void* stream);
+/* Training-mode BatchNormalization over the rows of an (m, c) view of an NHWC tensor (m = N H W), eps inside the root.
+ * cn_bn_train_coef: from s1 = sum x, s2 = sum x^2 per channel (cn_nc_reduce), mean = s1 / m, var = s2 / m - mean^2 (biased),
+ * r = rsqrt(var + eps), a = gamma r, b = beta - mean a, written to mean / var / r / a / b (c floats each).  A channel with
+ * mean^2 > 1000 (var + eps) -- the rule of cn_norm_coef_fwd -- takes mean and var from a second walk over x instead.  moving_mean /
+ * moving_var (may be NULL) are updated in place as Keras does, v -= (v - batch) (float)(1 - momentum) with the difference taken in
+ * double as Python does (1 - 0.99f in fp32 is 0.00999999, and a mean of 1000 shows it), the variance with the factor
+ * m / (m - 1) if bessel (the fused path of the 4-D layers).
+ * cn_bn_train_apply: y = act(a[c] x + b[c]), act CN_ACT_NONE or CN_ACT_RELU6.
+ * cn_bn_train_bwd_reduce: with g = gy 1[0 < y < 6] (CN_ACT_RELU6; y is not read for CN_ACT_NONE) and xh = (x - mean) r, per-slice
+ * partials part (slices, 2 c) = [sum g | sum g xh], plain stores, slices = cn_bn_train_bwd_slices(m, c); added in slice order by the
+ * caller as above into sums (2 c) = [d beta | d gamma].
+ * cn_bn_train_bwd_apply: gx = a (g - (d beta + xh d gamma) / m). */
+int cn_bn_train_coef(const float* s1, const float* s2, const float* gamma, const float* beta, const float* x, float* mean, float* var,
+                     float* r, float* a, float* b, float* moving_mean, float* moving_var, long long m, int c, float eps,
+                     double momentum, int bessel, void* stream);
+int cn_bn_train_apply(const float* x, const float* a, const float* b, float* y, long long m, int c, int act, void* stream);
+int cn_bn_train_bwd_slices(long long m, int c);
+int cn_bn_train_bwd_reduce(const float* gy, const float* y, const float* x, const float* mean, const float* r, float* part, int slices,
+                           long long m, int c, int act, void* stream);
+int cn_bn_train_bwd_apply(const float* gy, const float* y, const float* x, const float* mean, const float* r, const float* a,
+                          const float* sums, float* gx, long long m, int c, int act, void* stream);
 /* y[...,j] = scale * x[...,perm[j]] + off[j] on 3-channel images: (x+1)*127.5 + "caffe"/VGGFace
  * preprocessing (perceptual_loss.py:52-61 ; real_encoder.py:24-25); bwd scatters back. */
 int cn_chan_affine3_fwd(const float* x, float* y, size_t pixels, const int* perm, float scale, const float* off, void* stream);
