@@ -8,5 +8,6 @@ from .confignet_second_stage import ConfigNet
 from .latent_gan import LatentGAN
 from .confignet_utils import load_confignet
 from .synthetic_data import SyntheticFaceDataset
+from .face_image_normalizer import FaceImageNormalizer
 
-__all__ = ["ConfigNetFirstStage", "ConfigNet", "LatentGAN", "load_confignet", "SyntheticFaceDataset"]
+__all__ = ["ConfigNetFirstStage", "ConfigNet", "LatentGAN", "load_confignet", "SyntheticFaceDataset", "FaceImageNormalizer"]

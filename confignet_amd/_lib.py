@@ -162,6 +162,9 @@ SIGNATURES = {
     "cn_hdri_rows_v": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "cn_hdri_rows_h": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
     "cn_exp2m1": [_p, _p, _z, _p],
+    "cn_warp_affine_u8": [_p] * 6 + [_i] * 6 + [_p],
+    "cn_warp_nearest_f32": [_p] * 6 + [_i] * 6 + [_p],
+    "cn_eye_mask": [_p, _p, _z, _i] + [_f] * 6 + [_p],
     "cn_spin": [ctypes.c_ulonglong, _p],
     "cn_conv_weight_prep_bf16": [_p, _p, _p, _i, _i, _i, _p],
     "cn_conv_fwd_bf16": [_G, _p, _p, _p, _p, _i, _f, _p],

@@ -1,8 +1,15 @@
 """The dataset side of the step API (reference: confignet/neural_renderer_dataset.py): the two sampling distributions
-that a checkpoint's `<name>_facemodel_distr.pck` pickles, and a reader for the reference's dataset files
-(`<name>.pck` + `<name>_imgs.dat`) exposing the fields the step functions read (`.imgs`, `.eye_masks`,
-`.metadata_inputs`, `.metadata_input_distributions`).  Dataset CREATION (OpenFace alignment, UV-map eye masks,
-Inception features; l.102-140,236-330) is out of scope."""
+that a checkpoint's `<name>_facemodel_distr.pck` pickles, and the dataset itself -- read from the reference's files
+(`<name>.pck` + `<name>_imgs.dat`) or created here from a directory of pictures (generate_face_dataset: face normalisation,
+UV-map eye masks, CelebA attributes, Inception features; l.102-148, 230-335), in the same two files with the reference's
+class path, so either side loads what the other wrote.
+
+cv2 is not installed: pictures go through Pillow and are held in cv2's B, G, R order, UV maps through confignet_amd/exr.py.
+`device=None` runs the image arithmetic in numpy, a torch device string runs it in csrc/dataset.hip; both give the same bytes.
+The Inception features need the GPU either way (InceptionFeatureExtractor), unless a feature extractor is passed in."""
+import glob
+import json
+import ntpath
 import os
 import pickle
 from collections import OrderedDict
@@ -98,11 +105,47 @@ def dump_pickle(obj, path):
             sys.modules.pop(modname, None)
 
 
+class EyeRegionSpec:
+    """Where the two eyes lie in the UV space of the face model behind the synthetic renders: u ranges of the left and the right
+    eye, one v range for both (the reference's constants)"""
+    eye_region_max_y = 0.15
+    eye_region_min_y = 0.07
+
+    l_eye_region_max_x = 0.16
+    l_eye_region_min_x = 0.09
+    r_eye_region_max_x = 0.91
+    r_eye_region_min_x = 0.84
+
+    @classmethod
+    def bounds(cls):
+        """(l_min, l_max, r_min, r_max, y_min, y_max) as float32: what a float32 UV map is compared with"""
+        return tuple(np.float32(v) for v in (cls.l_eye_region_min_x, cls.l_eye_region_max_x, cls.r_eye_region_min_x,
+                                             cls.r_eye_region_max_x, cls.eye_region_min_y, cls.eye_region_max_y))
+
+
+def eye_mask_from_uv(uv_img, device=None):
+    """neural_renderer_dataset.py:246-253 for one (h, w, c) or a batch (n, h, w, c) of float32 UV maps in cv2's channel order
+    (channel 0 the file's B = u, channel 1 its G = v): uint8, 1 strictly inside the left or the right eye rectangle."""
+    uv_img = np.asarray(uv_img, np.float32)
+    l_min, l_max, r_min, r_max, y_min, y_max = EyeRegionSpec.bounds()
+    if device is not None:
+        import torch
+        from . import ops
+        dev = torch.device(device)
+        with torch.cuda.device(dev):
+            return ops.eye_mask(torch.from_numpy(np.ascontiguousarray(uv_img)).to(dev), (l_min, l_max, r_min, r_max, y_min, y_max)).cpu().numpy()
+    u, v = uv_img[..., 0], uv_img[..., 1]
+    in_y = (v < y_max) & (v > y_min)
+    return (in_y & (((u < l_max) & (u > l_min)) | ((u < r_max) & (u > r_min)))).astype(np.uint8)
+
+
 class NeuralRendererDataset:
-    """Reader of the reference's dataset files.  Attribute names are the pickled ones (l.71-100)."""
+    """The training data of the ConfigNet stages and of the attribute classifier: pictures (a uint8 memmap), and per picture what
+    was made with them.  Attribute names are the ones the reference pickles (l.71-100)."""
+    READ_CHUNK = 64                 # files decoded at a time while the dataset is written
 
     def __init__(self, img_shape=None, is_synthetic=True, head_rotation_range=((-30, 30), (-10, 10), (0, 0)),
-                 eye_rotation_range=((-25, 25), (-15, 15), (0, 0))):
+                 eye_rotation_range=((-25, 25), (-15, 15), (0, 0)), device=None):
         self.img_shape = img_shape
         self.is_synthetic = is_synthetic
         self.head_rotation_range = np.array(head_rotation_range)
@@ -118,6 +161,114 @@ class NeuralRendererDataset:
         self.metadata_inputs = None
         self.metadata_input_distributions = None
         self.metadata_input_labels = None
+        self._device = device       # where generate_face_dataset does its image arithmetic; not pickled
+
+    def __getstate__(self):
+        """What the reference pickles: no trace of this side's device."""
+        state = dict(self.__dict__)
+        state.pop("_device", None)
+        return state
+
+    def generate_face_dataset(self, input_dir, output_path, attribute_label_file_path=None, pre_normalize=True,
+                              openface_path=None, feature_extractor=None):
+        """The dataset of the pictures in input_dir, written to output_path (`<name>.pck`) and `<name>_imgs.dat` beside it:
+        normalise the directory, drop renders whose pose is out of range (synthetic data), then per picture its CelebA attributes
+        (when a list is given), its pixels and the eye mask of its warped UV map; Inception features of all pictures at the end.
+        openface_path: the user's FaceLandmarkImg (default: face_image_normalizer.DEFAULT_OPENFACE_PATH); feature_extractor:
+        anything with get_features((n, h, w, 3) uint8) -> (n, 2048), default InceptionFeatureExtractor on the GPU."""
+        from . import dataset_utils, exr, face_image_normalizer as fin
+        device = getattr(self, "_device", None)
+        fin.FaceImageNormalizer.normalize_dataset_dir(input_dir, pre_normalize, self.img_shape,
+                                                      openface_path=openface_path or fin.DEFAULT_OPENFACE_PATH, device=device)
+        paths = glob.glob(os.path.join(input_dir, "normalized", "*.png"))
+        if self.is_synthetic:
+            paths, self.render_metadata = self._remove_samples_with_out_of_range_pose(paths, self._load_metadata(paths))
+        celeba = None if attribute_label_file_path is None else dataset_utils.parse_celeba_attribute_file(attribute_label_file_path)
+        if celeba is not None:
+            self.attributes = [celeba[ntpath.basename(path).split(".")[0]] for path in paths]
+
+        self._initialize_imgs_memmap(len(paths), output_path)
+        masks = []
+        for begin in range(0, len(paths), self.READ_CHUNK):
+            print("reading pictures: %d of %d" % (begin, len(paths)))
+            chunk = paths[begin:begin + self.READ_CHUNK]
+            for k, img in enumerate(fin.thread_map(fin.imread, chunk)):
+                self.imgs[begin + k] = img
+            if self.is_synthetic:
+                uv_maps = fin.thread_map(exr.imread, [self._uv_map_path(path) for path in chunk])
+                masks.extend(eye_mask_from_uv(np.stack(uv_maps), device))
+        if self.is_synthetic:
+            self.eye_masks = np.array(masks)
+        self._compute_inception_features(feature_extractor)
+        self.save(output_path)
+
+    def _initialize_imgs_memmap(self, n_images, output_path):
+        """`<name>_imgs.dat` next to `<name>.pck`: raw uint8, (n_images, *img_shape), opened for writing"""
+        folder, name = os.path.split(output_path)
+        self.imgs_memmap_filename = os.path.splitext(name)[0] + "_imgs.dat"
+        self.imgs_memmap_dtype = np.uint8
+        self.imgs_memmap_shape = (n_images,) + tuple(self.img_shape)
+        self.imgs = np.memmap(os.path.join(folder, self.imgs_memmap_filename), dtype=np.uint8, mode="w+", shape=self.imgs_memmap_shape)
+
+    def _load_metadata(self, image_paths):
+        """The render metadata of normalized/img<rest>.png is meta<rest>.json one directory up (l.230-239)."""
+        render_metadata = []
+        for path in image_paths:
+            head, tail = os.path.split(os.path.splitext(path)[0])
+            with open(os.path.join(head, "..", "meta" + tail[3:] + ".json")) as fp:
+                render_metadata.append(json.load(fp))
+        return render_metadata
+
+    @staticmethod
+    def _uv_map_path(image_path):
+        head, tail = os.path.split(os.path.splitext(image_path)[0])
+        return os.path.join(head, "uv" + tail[3:] + ".exr")
+
+    def _get_eye_mask_for_image_path(self, image_path):
+        from . import exr
+        return eye_mask_from_uv(exr.imread(self._uv_map_path(image_path)), getattr(self, "_device", None))
+
+    def _remove_samples_with_out_of_range_pose(self, image_paths, metadata):
+        """Keeps the renders whose head and left-eye rotation lie inside the dataset's ranges.  The ranges are in degrees in
+        ConfigNet's axis order; the render metadata holds radians with the axes in the order [1, 2, 0] of that."""
+        head_bounds = np.deg2rad(self.head_rotation_range[[1, 2, 0]])
+        eye_bounds = np.deg2rad(self.eye_rotation_range[[1, 2, 0]])
+
+        def inside(pose, bounds):
+            return np.all(pose >= bounds[:, 0]) and np.all(pose <= bounds[:, 1])
+
+        kept = [i for i, md in enumerate(metadata)
+                if inside(md["bone_rotations"]["head"], head_bounds) and inside(md["bone_rotations"]["left_eye"], eye_bounds)]
+        return [image_paths[i] for i in kept], [metadata[i] for i in kept]
+
+    def write_images(self, directory, draw_landmarks=False):
+        """neural_renderer_dataset.py:281-296 (the reference's draw_landmarks reads a `.landmarks` field that no dataset has)."""
+        from .face_image_normalizer import imwrite
+        assert not draw_landmarks, "datasets hold no landmarks"
+        os.makedirs(directory, exist_ok=True)
+        for i, img in enumerate(self.imgs):
+            imwrite(os.path.join(directory, "%05d.jpg" % i), img)
+        imwrite(os.path.join(directory, "mean_img.jpg"), np.mean(self.imgs, axis=0).astype(np.uint8))
+
+    def write_images_by_attribute(self, directory):
+        """One folder per attribute under `directory`, holding a JPEG of every picture that has the attribute"""
+        from .face_image_normalizer import imwrite
+        assert self.attributes is not None
+        names = list(self.attributes[0])
+        assert all(list(a) == names for a in self.attributes)
+        for name in names:
+            folder = os.path.join(directory, name)
+            os.makedirs(folder, exist_ok=True)
+            for i, a in enumerate(self.attributes):
+                if a[name]:
+                    imwrite(os.path.join(folder, "%06d.jpg" % i), self.imgs[i])
+
+    def _compute_inception_features(self, feature_extractor=None):
+        """neural_renderer_dataset.py:323-325; get_features takes the whole array and walks it in chunks."""
+        if feature_extractor is None:
+            from .metrics.inception_distance import InceptionFeatureExtractor
+            feature_extractor = InceptionFeatureExtractor(self.imgs.shape[1:])
+        self.inception_features = feature_extractor.get_features(self.imgs)
 
     @staticmethod
     def load(filename):
@@ -130,12 +281,19 @@ class NeuralRendererDataset:
         return dataset
 
     def save(self, filename):
-        """neural_renderer_dataset.py:332-341 (the image memmap is written separately and never pickled)."""
+        """neural_renderer_dataset.py:327-335: the image memmap is flushed and never pickled; one that was being written is
+        opened again read-only, as the reference does."""
         imgs, self.imgs = self.imgs, None
+        writing = isinstance(imgs, np.memmap) and imgs.mode != "r"
         try:
+            if writing:
+                imgs.flush()
             dump_pickle(self, filename)
         finally:
             self.imgs = imgs
+        if writing:
+            path = os.path.join(os.path.dirname(filename), self.imgs_memmap_filename)
+            self.imgs = np.memmap(path, self.imgs_memmap_dtype, "r", shape=tuple(self.imgs_memmap_shape))
 
     def get_attribute_values(self, sample_idxs, attribute_names):
         """neural_renderer_dataset.py:312-321: (len(sample_idxs), len(attribute_names)) array of the per-image CelebA attributes."""
@@ -202,4 +360,4 @@ class NeuralRendererDataset:
 
 
 _CLASSES = {"OneHotDistribution": OneHotDistribution, "ExemplarDistribution": ExemplarDistribution,
-            "NeuralRendererDataset": NeuralRendererDataset}
+            "NeuralRendererDataset": NeuralRendererDataset, "EyeRegionSpec": EyeRegionSpec}

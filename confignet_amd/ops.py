@@ -1631,6 +1631,52 @@ def exp2m1(x):
     return y
 
 
+def _warp_tables(tables, n, oh, ow):
+    x0, y0, adelta, bdelta = tables
+    assert tuple(x0.shape) == (n, oh) and tuple(y0.shape) == (n, oh), "x0, y0: one int32 per image and output row"
+    assert tuple(adelta.shape) == (n, ow) and tuple(bdelta.shape) == (n, ow), "adelta, bdelta: one int32 per image and output column"
+    return [_i32ptr(t) for t in tables]
+
+
+def warp_affine_u8(src, tables, oh, ow, out=None):
+    """cn_warp_affine_u8: cv2.warpAffine (bilinear, constant border 0) of src (n, sh, sw, c) uint8 into (n, oh, ow, c), one
+    transform per image as int32 tables (x0 (n, oh), y0 (n, oh), adelta (n, ow), bdelta (n, ow):
+    face_image_normalizer.affine_tables with delta 16)."""
+    src = _c(src)
+    n, sh, sw, c = src.shape
+    assert src.dtype == torch.uint8
+    ptrs = _warp_tables(tables, n, oh, ow)
+    if out is None:
+        out = torch.empty((n, oh, ow, c), device=src.device, dtype=torch.uint8)
+    assert out.dtype == torch.uint8 and tuple(out.shape) == (n, oh, ow, c)
+    check(lib.cn_warp_affine_u8(_ptr(src), _ptr(out), *ptrs, n, sh, sw, c, oh, ow, _stream()), "cn_warp_affine_u8")
+    return out
+
+
+def warp_nearest_f32(src, tables, oh, ow, out=None):
+    """cn_warp_nearest_f32: cv2.warpAffine(flags=INTER_NEAREST) of src (n, sh, sw, c) float32 (tables built with delta 512)."""
+    src = _c(src)
+    n, sh, sw, c = src.shape
+    ptrs = _warp_tables(tables, n, oh, ow)
+    if out is None:
+        out = torch.empty((n, oh, ow, c), device=src.device, dtype=torch.float32)
+    assert tuple(out.shape) == (n, oh, ow, c)
+    check(lib.cn_warp_nearest_f32(_fptr(src), _fptr(out), *ptrs, n, sh, sw, c, oh, ow, _stream()), "cn_warp_nearest_f32")
+    return out
+
+
+def eye_mask(uv, bounds, out=None):
+    """cn_eye_mask: uv (..., h, w, c >= 2) float32 -> (..., h, w) uint8, 1 where the first two channels lie strictly inside the left
+    or the right eye rectangle; bounds = (l_min, l_max, r_min, r_max, y_min, y_max)."""
+    uv = _c(uv)
+    c = uv.shape[-1]
+    if out is None:
+        out = torch.empty(uv.shape[:-1], device=uv.device, dtype=torch.uint8)
+    assert out.dtype == torch.uint8 and out.numel() == uv.numel() // c and len(bounds) == 6
+    check(lib.cn_eye_mask(_fptr(uv), _ptr(out), out.numel(), c, *[float(b) for b in bounds], _stream()), "cn_eye_mask")
+    return out
+
+
 def to_uint8(x):
     x = f32(x)
     out = torch.empty(x.shape, device=x.device, dtype=torch.uint8)

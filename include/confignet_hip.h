@@ -581,6 +581,26 @@ int cn_hdri_rows_h(const float* v, float* out, const int* idx, const int* shift,
 /* y = exp2f(x) - 1 (HDRIModelPCA.inverse_transform: np.power(2, x) - 1) */
 int cn_exp2m1(const float* x, float* y, size_t numel, void* stream);
 
+/* ---- dataset creation (confignet/face_image_normalizer.py:113-126, neural_renderer_dataset.py:241-255;
+ * confignet_amd/face_image_normalizer.py) --------------------------------------------------------------------------------------
+ * cv2.warpAffine(img, M, dsize) with the defaults (bilinear, BORDER_CONSTANT 0) for n uint8 images (n, sh, sw, c), c = 1 .. 4
+ * interleaved channels, into dst (n, oh, ow, c), one transform per image.  The transform arrives as cv2's own int32 tables with
+ * 10 fractional bits (face_image_normalizer.affine_tables, delta = 16): x0, y0 (n, oh) per output row, adelta, bdelta (n, ow)
+ * per output column.  X = (x0[y] + adelta[x]) >> 5, sx = X >> 5, ax = X & 31 (Y, sy, ay likewise); the taps (sy, sx) ..
+ * (sy + 1, sx + 1), 0 outside the source, with the weights 32 (32 - ax)(32 - ay), 32 ax (32 - ay), 32 (32 - ax) ay, 32 ax ay;
+ * out = (sum + 16384) >> 15.  Integer-only; the table sum is taken in 64 bits and every tap is tested against the source, so no
+ * table entry reads out of bounds.  sh, sw <= 32767 (cv2 keeps source coordinates as int16); all pointers are device memory. */
+int cn_warp_affine_u8(const uint8_t* src, uint8_t* dst, const int* x0, const int* y0, const int* adelta, const int* bdelta,
+                      int n, int sh, int sw, int c, int oh, int ow, void* stream);
+/* the INTER_NEAREST form for float32 images (the UV maps): the same tables built with delta = 512, sx = (x0[y] + adelta[x]) >> 10,
+ * sy likewise; dst = src[sy][sx], 0.0 outside */
+int cn_warp_nearest_f32(const float* src, float* dst, const int* x0, const int* y0, const int* adelta, const int* bdelta,
+                        int n, int sh, int sw, int c, int oh, int ow, void* stream);
+/* mask[i] = 1 where pixel i of uv (pixels, c >= 2) has l_min < u < l_max or r_min < u < r_max, and y_min < v < y_max (u, v: its
+ * first two channels; strict float32 comparisons, NaN is outside), else 0 */
+int cn_eye_mask(const float* uv, uint8_t* mask, size_t pixels, int c, float l_min, float l_max, float r_min, float r_max,
+                float y_min, float y_max, void* stream);
+
 /* ---- profiling of the dominant kernel class (implicit-GEMM convolutions) with HIP events
  * recorded on the launch stream (bench.py roofline object) -----------------------------------*/
 int cn_prof_enable(int on);
