@@ -145,6 +145,7 @@ SIGNATURES = {
     "cn_bn_train_coef": [_p] * 12 + [ctypes.c_longlong, _i, _f, ctypes.c_double, _i, _p],
     "cn_bn_train_apply": [_p, _p, _p, _p, ctypes.c_longlong, _i, _i, _p],
     "cn_bn_train_bwd_slices": [ctypes.c_longlong, _i],
+    "cn_chan_slices_plan": [ctypes.c_longlong, _i, _i, ctypes.POINTER(ctypes.c_int * 5)],
     "cn_bn_train_bwd_reduce": [_p] * 6 + [_i, ctypes.c_longlong, _i, _i, _p],
     "cn_bn_train_bwd_apply": [_p] * 8 + [ctypes.c_longlong, _i, _i, _p],
     "cn_chan_affine3_fwd": [_p, _p, _z, ctypes.POINTER(_i), _f, ctypes.POINTER(_f), _p],

@@ -8,7 +8,7 @@
 // What the existing launches did not cover, and why these four exist: cn_nc_lin2 has ReLU but no ReLU6 behind its affine map;
 // act_deriv (cn_bn_act_bwd, cn_nc_reduce_dact) knows no two-sided mask, and those sum g x with the RAW x, which cancels for a
 // channel with |mean| >> sigma where sum g (x - mean) r does not; cn_norm_apply's grid is sized per sample and the view has one.
-#include "common.h"
+#include "chan_slices.h"
 
 namespace {
 
@@ -86,38 +86,8 @@ __global__ __launch_bounds__(256) void bn_train_apply_kernel(const float* __rest
     }
 }
 
-// The backward reduce pass: 256 threads as TX channel groups x TY row lanes over a slice of rows, the lanes of a channel group
-// combined in LDS (the layout of dwconv3x3_wgrad_kernel: float4 stores of consecutive lanes, dword reads of consecutive threads),
-// per-slice partials [sum g | sum g xh] left with plain stores and added by the caller in slice order.
-struct BnPlan {
-    int TX, TY, cb, slices;
-    long per_slice;
-};
-
-BnPlan bn_bwd_plan(long m, int cgs) {
-    BnPlan p;
-    p.TX = 1;
-    while (p.TX < cgs && p.TX < 64) p.TX *= 2;
-    p.TY = 256 / p.TX;
-    p.cb = cn_cdiv(cgs, p.TX);
-    long slices = (m + 4L * p.TY - 1) / (4L * p.TY);       // at least 4 rows per lane
-    const long cap = 1024 / p.cb > 1 ? 1024 / p.cb : 1;  // up to 4 workgroups per compute unit
-    if (slices > cap) slices = cap;
-    p.per_slice = (m + slices - 1) / slices;
-    p.slices = (int)((m + p.per_slice - 1) / p.per_slice);
-    return p;
-}
-
-template <int V>
-__device__ __forceinline__ void ldv(const float* p, float* v) {
-    if (V == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        v[0] = t.x; v[1 % V] = t.y; v[2 % V] = t.z; v[3 % V] = t.w;
-    } else {
-        v[0] = *p;
-    }
-}
-
+// The backward reduce pass: a per-channel reduction over slices of the rows (chan_slices.h: the work split, the slice rule, the
+// lane combine), per-slice partials [sum g | sum g xh] left with plain stores and added by the caller in slice order.
 template <int V>
 __global__ __launch_bounds__(256) void bn_train_bwd_reduce_kernel(const float* __restrict__ gy, const float* __restrict__ y,
                                                                   const float* __restrict__ x, const float* __restrict__ mean,
@@ -126,44 +96,31 @@ __global__ __launch_bounds__(256) void bn_train_bwd_reduce_kernel(const float* _
     __shared__ float red[2 * 256 * V];
     const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x / TX;
     const int ch = (blockIdx.x * TX + tx) * V;
-    float sg[V], sx[V];
+    float acc[2][V];                                   // sum g | sum g xh
 #pragma unroll
-    for (int e = 0; e < V; ++e) sg[e] = sx[e] = 0.f;
+    for (int e = 0; e < V; ++e) acc[0][e] = acc[1][e] = 0.f;
     if (ch < c) {
         float mu[V], rs[V];
-        ldv<V>(mean + ch, mu);
-        ldv<V>(r + ch, rs);
+        VecIO<V>::ld(mean + ch, mu);
+        VecIO<V>::ld(r + ch, rs);
         const long r0 = blockIdx.y * per_slice, r1 = r0 + per_slice < m ? r0 + per_slice : m;
         for (long i = r0 + ty; i < r1; i += TY) {
             float g[V], xv[V], yv[V];
-            ldv<V>(gy + i * c + ch, g);
-            ldv<V>(x + i * c + ch, xv);
+            VecIO<V>::ld(gy + i * c + ch, g);
+            VecIO<V>::ld(x + i * c + ch, xv);
             if (act == CN_ACT_RELU6) {
-                ldv<V>(y + i * c + ch, yv);
+                VecIO<V>::ld(y + i * c + ch, yv);
 #pragma unroll
                 for (int e = 0; e < V; ++e) g[e] *= relu6_mask(yv[e], act);
             }
 #pragma unroll
             for (int e = 0; e < V; ++e) {
-                sg[e] += g[e];
-                sx[e] = fmaf(g[e], (xv[e] - mu[e]) * rs[e], sx[e]);
+                acc[0][e] += g[e];
+                acc[1][e] = fmaf(g[e], (xv[e] - mu[e]) * rs[e], acc[1][e]);
             }
         }
     }
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-        red[(long)threadIdx.x * V + e] = sg[e];
-        red[(256 + (long)threadIdx.x) * V + e] = sx[e];
-    }
-    __syncthreads();
-    const int W = TX * V;
-    for (int o = threadIdx.x; o < 2 * W; o += 256) {
-        const int k = o / W, cl = o - k * W;
-        float s = 0.f;
-        for (int q = 0; q < TY; ++q) s += red[(k * TY + q) * W + cl];
-        const int co = blockIdx.x * W + cl;
-        if (co < c) part[((long)blockIdx.y * 2 + k) * c + co] = s;
-    }
+    chan_lanes_sum<2, V>(acc, red, part, c, TX, TY);
 }
 
 template <int V>
@@ -176,31 +133,38 @@ __global__ __launch_bounds__(256) void bn_train_bwd_apply_kernel(const float* __
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total_g; i += (long)gridDim.x * 256) {
         const int ch = (int)(i % cgs) * V;
         float g[V], xv[V], yv[V], mu[V], rs[V], av[V], db[V], dg[V], o[V];
-        ldv<V>(gy + i * V, g);
-        ldv<V>(x + i * V, xv);
-        ldv<V>(mean + ch, mu);
-        ldv<V>(r + ch, rs);
-        ldv<V>(a + ch, av);
-        ldv<V>(sums + ch, db);
-        ldv<V>(sums + c + ch, dg);
+        VecIO<V>::ld(gy + i * V, g);
+        VecIO<V>::ld(x + i * V, xv);
+        VecIO<V>::ld(mean + ch, mu);
+        VecIO<V>::ld(r + ch, rs);
+        VecIO<V>::ld(a + ch, av);
+        VecIO<V>::ld(sums + ch, db);
+        VecIO<V>::ld(sums + c + ch, dg);
         if (act == CN_ACT_RELU6) {
-            ldv<V>(y + i * V, yv);
+            VecIO<V>::ld(y + i * V, yv);
 #pragma unroll
             for (int e = 0; e < V; ++e) g[e] *= relu6_mask(yv[e], act);
         }
 #pragma unroll
         for (int e = 0; e < V; ++e) o[e] = av[e] * (g[e] - (db[e] + (xv[e] - mu[e]) * rs[e] * dg[e]) * inv_m);
-        if (V == 4) *reinterpret_cast<float4*>(gx + i * 4) = make_float4(o[0], o[1 % V], o[2 % V], o[3 % V]);
-        else gx[i] = o[0];
+        VecIO<V>::st(gx + i * V, o);
     }
 }
 
-unsigned ew_blocks(long total_g) {
-    const long b = (total_g + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
+// The launch of an elementwise pass over (m, c): float4 groups where c % 4 == 0 and every operand is 16-byte aligned, else scalars;
+// total_g groups, a grid-stride loop of at most 8192 workgroups.
+struct EwShape {
+    bool v4;
+    long total_g;
+    unsigned blocks;
+};
 
-bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
+template <typename... P>
+EwShape ew_shape(long m, int c, const P*... operands) {
+    const bool v4 = c % 4 == 0 && aligned16(operands...);
+    const long total_g = m * (v4 ? c / 4 : c), b = (total_g + 255) / 256;
+    return {v4, total_g, (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b))};
+}
 
 }  // namespace
 
@@ -220,20 +184,25 @@ extern "C" int cn_bn_train_apply(const float* x, const float* a, const float* b,
     CN_CHECK_ARG(m > 0 && c > 0, "cn_bn_train_apply: bad extents m %lld c %d", m, c);
     CN_CHECK_ARG(act == CN_ACT_NONE || act == CN_ACT_RELU6, "cn_bn_train_apply: activation %d", act);
     hipStream_t s = (hipStream_t)stream;
-    if (c % 4 == 0 && aligned16(x) && aligned16(a) && aligned16(b) && aligned16(y)) {
-        const long tg = (long)m * (c / 4);
-        hipLaunchKernelGGL(bn_train_apply_kernel<4>, dim3(ew_blocks(tg)), dim3(256), 0, s, x, a, b, y, tg, c, act);
-    } else {
-        const long tg = (long)m * c;
-        hipLaunchKernelGGL(bn_train_apply_kernel<1>, dim3(ew_blocks(tg)), dim3(256), 0, s, x, a, b, y, tg, c, act);
-    }
+    const EwShape e = ew_shape((long)m, c, x, a, b, y);
+    if (e.v4) hipLaunchKernelGGL(bn_train_apply_kernel<4>, dim3(e.blocks), dim3(256), 0, s, x, a, b, y, e.total_g, c, act);
+    else hipLaunchKernelGGL(bn_train_apply_kernel<1>, dim3(e.blocks), dim3(256), 0, s, x, a, b, y, e.total_g, c, act);
     CN_LAUNCH_CHECK();
     return CN_OK;
 }
 
 extern "C" int cn_bn_train_bwd_slices(long long m, int c) {
     CN_CHECK_ARG(m > 0 && c > 0, "cn_bn_train_bwd_slices: bad extents");
-    return bn_bwd_plan((long)m, c % 4 == 0 ? c / 4 : c).slices;
+    return chan_slices_plan((long)m, c % 4 == 0 ? c / 4 : c, 0).slices;
+}
+
+extern "C" int cn_chan_slices_plan(long long rows, int c, int min_rows, int* out5) {
+    CN_CHECK_ARG(rows > 0 && c > 0 && min_rows >= 0 && out5, "cn_chan_slices_plan: bad args");
+    const ChanSlicesPlan p = chan_slices_plan((long)rows, c % 4 == 0 ? c / 4 : c, min_rows);
+    CN_CHECK_ARG(p.per_slice <= 0x7fffffffL, "cn_chan_slices_plan: %ld rows per slice do not fit the report", p.per_slice);
+    const int v[5] = {p.TX, p.TY, p.cb, p.slices, (int)p.per_slice};
+    for (int i = 0; i < 5; ++i) out5[i] = v[i];
+    return CN_OK;
 }
 
 extern "C" int cn_bn_train_bwd_reduce(const float* gy, const float* y, const float* x, const float* mean, const float* r, float* part,
@@ -243,10 +212,10 @@ extern "C" int cn_bn_train_bwd_reduce(const float* gy, const float* y, const flo
     CN_CHECK_ARG(act == CN_ACT_NONE || (act == CN_ACT_RELU6 && y), "cn_bn_train_bwd_reduce: activation %d (ReLU6 needs y)", act);
     hipStream_t s = (hipStream_t)stream;
     const bool v4 = c % 4 == 0;
-    const BnPlan p = bn_bwd_plan((long)m, v4 ? c / 4 : c);
+    const ChanSlicesPlan p = chan_slices_plan((long)m, v4 ? c / 4 : c, 0);
     CN_CHECK_ARG(slices == p.slices, "cn_bn_train_bwd_reduce: %d slices given, the plan has %d (cn_bn_train_bwd_slices)", slices, p.slices);
     if (v4) {
-        CN_CHECK_ARG(aligned16(gy) && aligned16(x) && aligned16(y) && aligned16(mean) && aligned16(r),
+        CN_CHECK_ARG(aligned16(gy, x, y, mean, r),
                      "cn_bn_train_bwd_reduce: operands must be 16-byte aligned when c %% 4 == 0");
         hipLaunchKernelGGL(bn_train_bwd_reduce_kernel<4>, dim3(p.cb, p.slices), dim3(256), 0, s, gy, y, x, mean, r, part, (long)m, c,
                            p.per_slice, p.TX, p.TY, act);
@@ -265,14 +234,9 @@ extern "C" int cn_bn_train_bwd_apply(const float* gy, const float* y, const floa
     CN_CHECK_ARG(act == CN_ACT_NONE || (act == CN_ACT_RELU6 && y), "cn_bn_train_bwd_apply: activation %d (ReLU6 needs y)", act);
     hipStream_t s = (hipStream_t)stream;
     const float inv_m = 1.f / (float)m;
-    if (c % 4 == 0 && aligned16(gy) && aligned16(y) && aligned16(x) && aligned16(mean) && aligned16(r) && aligned16(a) && aligned16(sums) &&
-        aligned16(gx)) {
-        const long tg = (long)m * (c / 4);
-        hipLaunchKernelGGL(bn_train_bwd_apply_kernel<4>, dim3(ew_blocks(tg)), dim3(256), 0, s, gy, y, x, mean, r, a, sums, gx, tg, c, inv_m, act);
-    } else {
-        const long tg = (long)m * c;
-        hipLaunchKernelGGL(bn_train_bwd_apply_kernel<1>, dim3(ew_blocks(tg)), dim3(256), 0, s, gy, y, x, mean, r, a, sums, gx, tg, c, inv_m, act);
-    }
+    const EwShape e = ew_shape((long)m, c, gy, y, x, mean, r, a, sums, gx);
+    if (e.v4) hipLaunchKernelGGL(bn_train_bwd_apply_kernel<4>, dim3(e.blocks), dim3(256), 0, s, gy, y, x, mean, r, a, sums, gx, e.total_g, c, inv_m, act);
+    else hipLaunchKernelGGL(bn_train_bwd_apply_kernel<1>, dim3(e.blocks), dim3(256), 0, s, gy, y, x, mean, r, a, sums, gx, e.total_g, c, inv_m, act);
     CN_LAUNCH_CHECK();
     return CN_OK;
 }

@@ -2,7 +2,8 @@
 // the depthwise 3x3 convolution of keras MobileNetV2 (DepthwiseConv2D, depth_multiplier 1, with the folded BatchNormalization
 // as a per-channel bias and ReLU6 in the epilogue) and the one-pass image preprocessing in front of it (cv2.resize INTER_LINEAR +
 // keras.applications.mobilenet_v2.preprocess_input); for training, the depthwise convolution's input and filter gradients.
-#include "common.h"
+#include <type_traits>
+#include "chan_slices.h"
 
 namespace {
 
@@ -21,22 +22,6 @@ namespace {
 // 9 taps of its channels sit in registers; each input row it needs ((OPY - 1) S + 3 of them) is loaded ONCE, (OPX - 1) S + 3
 // pixels wide, and feeds every output row / column of the block that reads it -- 24 float4 loads for 8 outputs at stride 1
 // (instead of 72), 25 for 4 at stride 2 (instead of 36).
-template <int V>
-struct VecIO;
-template <>
-struct VecIO<4> {
-    static __device__ __forceinline__ void ld(const float* p, float* v) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    }
-    static __device__ __forceinline__ void st(float* p, const float* v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-};
-template <>
-struct VecIO<1> {
-    static __device__ __forceinline__ void ld(const float* p, float* v) { v[0] = *p; }
-    static __device__ __forceinline__ void st(float* p, const float* v) { *p = v[0]; }
-};
-
 template <int S, int V, int OPX, int OPY>
 __global__ __launch_bounds__(256) void dwconv3x3_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                         const float* __restrict__ bias, float* __restrict__ y, int h, int wd, int c,
@@ -118,18 +103,36 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const float* __restrict_
     }
 }
 
+// The geometry of one call by the padding rule above: output extents and low pads (the three launchers and the slices query).
+struct DwGeom {
+    int n, h, wd, c, oh, ow, ph, pw;
+};
+
+DwGeom dw_geom(int n, int h, int wd, int c, int stride) {
+    const int oh = (h + stride - 1) / stride, ow = (wd + stride - 1) / stride;
+    return {n, h, wd, c, oh, ow, ((oh - 1) * stride + 3 - h) / 2, ((ow - 1) * stride + 3 - wd) / 2};     // total >= 1 for k = 3, s <= 2
+}
+
+// f(S, V) as compile-time constants for stride 1 / 2 and 4 channels per lane or 1: the one place an entry point's (stride, vector
+// width) becomes an instantiation.
+template <int I>
+using Int = std::integral_constant<int, I>;
+
+template <typename F>
+int dw_instance(int stride, bool v4, F f) {
+    if (stride == 1) return v4 ? f(Int<1>{}, Int<4>{}) : f(Int<1>{}, Int<1>{});
+    return v4 ? f(Int<2>{}, Int<4>{}) : f(Int<2>{}, Int<1>{});
+}
+
 template <int S, int V, int OPX, int OPY>
-int launch_dw(const float* x, const float* w, const float* bias, float* y, int n, int h, int wd, int c, int act, float slope,
-              hipStream_t s) {
-    const int oh = (h + S - 1) / S, ow = (wd + S - 1) / S;
-    const int ph = ((oh - 1) * S + 3 - h) / 2, pw = ((ow - 1) * S + 3 - wd) / 2;     // total >= 1 for k = 3, s <= 2
-    const int nxb = cn_cdiv(ow, OPX), nyb = cn_cdiv(oh, OPY);
-    const long total = (long)n * nyb * nxb * (c / V);
+int launch_dw(const DwGeom& g, const float* x, const float* w, const float* bias, float* y, int act, float slope, hipStream_t s) {
+    const int nxb = cn_cdiv(g.ow, OPX), nyb = cn_cdiv(g.oh, OPY);
+    const long total = (long)g.n * nyb * nxb * (g.c / V);
     const int threads = 256;
     const long blocks = (total + threads - 1) / threads;
     CN_CHECK_ARG(blocks < 0x7fffffffL, "cn_dwconv3x3_fwd: tensor too large");
-    hipLaunchKernelGGL((dwconv3x3_kernel<S, V, OPX, OPY>), dim3((unsigned)blocks), dim3(threads), 0, s, x, w, bias, y, h, wd, c, oh, ow,
-                       ph, pw, nxb, nyb, total, act, slope);
+    hipLaunchKernelGGL((dwconv3x3_kernel<S, V, OPX, OPY>), dim3((unsigned)blocks), dim3(threads), 0, s, x, w, bias, y, g.h, g.wd, g.c, g.oh,
+                       g.ow, g.ph, g.pw, nxb, nyb, total, act, slope);
     CN_LAUNCH_CHECK();
     return CN_OK;
 }
@@ -223,52 +226,22 @@ __global__ __launch_bounds__(256) void dwconv3x3_dgrad_kernel(const float* __res
 }
 
 template <int S, int V, int IPX, int IPY>
-int launch_dw_dgrad(const float* gy, const float* w, float* gx, int n, int h, int wd, int c, hipStream_t s) {
-    const int oh = (h + S - 1) / S, ow = (wd + S - 1) / S;
-    const int ph = ((oh - 1) * S + 3 - h) / 2, pw = ((ow - 1) * S + 3 - wd) / 2;
-    const int nxb = cn_cdiv(wd + (S == 1 ? 0 : pw), IPX), nyb = cn_cdiv(h + (S == 1 ? 0 : ph), IPY);
-    const long total = (long)n * nyb * nxb * (c / V);
+int launch_dw_dgrad(const DwGeom& g, const float* gy, const float* w, float* gx, hipStream_t s) {
+    const int nxb = cn_cdiv(g.wd + (S == 1 ? 0 : g.pw), IPX), nyb = cn_cdiv(g.h + (S == 1 ? 0 : g.ph), IPY);
+    const long total = (long)g.n * nyb * nxb * (g.c / V);
     const long blocks = (total + 255) / 256;
     CN_CHECK_ARG(blocks < 0x7fffffffL, "cn_dwconv3x3_dgrad: tensor too large");
-    hipLaunchKernelGGL((dwconv3x3_dgrad_kernel<S, V, IPX, IPY>), dim3((unsigned)blocks), dim3(256), 0, s, gy, w, gx, h, wd, c, oh, ow, ph,
-                       pw, nxb, nyb, total);
+    hipLaunchKernelGGL((dwconv3x3_dgrad_kernel<S, V, IPX, IPY>), dim3((unsigned)blocks), dim3(256), 0, s, gy, w, gx, g.h, g.wd, g.c, g.oh,
+                       g.ow, g.ph, g.pw, nxb, nyb, total);
     CN_LAUNCH_CHECK();
     return CN_OK;
 }
 
 // ---- depthwise 3x3: filter gradient ------------------------------------------------------------------------------------------
-// gw[ky, kx, ch] = sum_{b, oy, ox} gy[b, oy, ox, ch] x[b, oy S - ph + ky, ox S - pw + kx, ch]: N OH OW terms into 9 C numbers.
-// 256 threads as TX channel groups x TY pixel lanes (TX = the channel groups rounded up to a power of two, 64 at most: lanes of a
-// wave on consecutive channel groups, coalesced NHWC rows as in the forward); a workgroup owns a SLICE of consecutive output
-// pixels, lane ty walks the pixels ty, ty + TY, ... of it with 9 x V accumulators in registers.  The TY lanes of a channel group
-// then combine in LDS: every lane stores its accumulators as red[k][ty][tx] (consecutive lanes -> consecutive float4: ds_write_b128
-// without bank conflicts), and after the barrier thread o sums the TY entries of output (k, channel) = o with consecutive threads on
-// consecutive dwords (conflict-free again), in ty order.  The workgroup leaves 9 x C partials with plain stores; the caller adds
-// the slices in slice order (cn_sum_rows_into, or the grouped reduction at the join of a backward pass).  No atomics anywhere: the
-// result has the same bits in every mode.
-// Slices (dw_wgrad_plan).  A slice costs 9 C floats written and read again next to 2 per_slice C floats of operands, so it holds at
-// least 64 pixels (<= 7 % extra traffic) and at least 4 pixels per lane; as many slices as that allows, up to 1024 workgroups
-// (4 per compute unit).  Batch 32: the 7 x 7 x 960 layer (1568 pixels, TX 64, TY 4, 4 channel blocks) gets 25 slices of 64 pixels,
-// 100 workgroups of 16 pixels per lane; the 128 x 128 x 32 layer (524 288 pixels, TX 8, TY 32, one channel block) gets 1024 slices
-// of 512 pixels.
-struct DwWgradPlan {
-    int TX, TY, cb, slices, per_slice;
-};
-
-DwWgradPlan dw_wgrad_plan(long pixels, int cgs) {
-    DwWgradPlan p;
-    p.TX = 1;
-    while (p.TX < cgs && p.TX < 64) p.TX *= 2;
-    p.TY = 256 / p.TX;
-    p.cb = cn_cdiv(cgs, p.TX);
-    const long min_px = 4L * p.TY > 64 ? 4L * p.TY : 64;
-    long slices = (pixels + min_px - 1) / min_px;
-    const long cap = 1024 / p.cb > 1 ? 1024 / p.cb : 1;
-    if (slices > cap) slices = cap;
-    p.per_slice = (int)((pixels + slices - 1) / slices);
-    p.slices = (int)((pixels + p.per_slice - 1) / p.per_slice);
-    return p;
-}
+// gw[ky, kx, ch] = sum_{b, oy, ox} gy[b, oy, ox, ch] x[b, oy S - ph + ky, ox S - pw + kx, ch]: N OH OW terms into 9 C numbers, as a
+// per-channel reduction over slices of the output pixels (chan_slices.h: the work split, the slice rule with a floor of 64 pixels
+// per slice, the lane combine): a lane keeps 9 x V accumulators, the workgroup leaves 9 x C partials, no atomics anywhere.
+constexpr long DW_WGRAD_MIN_ROWS = 64;
 
 template <int S, int V>
 __global__ __launch_bounds__(256) void dwconv3x3_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ gy,
@@ -308,29 +281,17 @@ __global__ __launch_bounds__(256) void dwconv3x3_wgrad_kernel(const float* __res
             }
         }
     }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) VecIO<V>::st(red + ((long)k * 256 + threadIdx.x) * V, acc[k]);
-    __syncthreads();
-    const int W = TX * V;                              // channels of this workgroup
-    for (int o = threadIdx.x; o < 9 * W; o += 256) {
-        const int k = o / W, cl = o - k * W;
-        float s = 0.f;
-        for (int y = 0; y < TY; ++y) s += red[(k * TY + y) * W + cl];
-        const int co = blockIdx.x * W + cl;
-        if (co < c) part[((long)blockIdx.y * 9 + k) * c + co] = s;
-    }
+    chan_lanes_sum<9, V>(acc, red, part, c, TX, TY);
 }
 
 template <int S, int V>
-int launch_dw_wgrad(const float* x, const float* gy, float* part, int slices, int n, int h, int wd, int c, hipStream_t s) {
-    const int oh = (h + S - 1) / S, ow = (wd + S - 1) / S;
-    const int ph = ((oh - 1) * S + 3 - h) / 2, pw = ((ow - 1) * S + 3 - wd) / 2;
-    const long pixels = (long)n * oh * ow;
-    CN_CHECK_ARG(pixels < 0x7fffffffL, "cn_dwconv3x3_wgrad: tensor too large");
-    const DwWgradPlan p = dw_wgrad_plan(pixels, c / V);
+int launch_dw_wgrad(const DwGeom& g, const float* x, const float* gy, float* part, int slices, hipStream_t s) {
+    const long pixels = (long)g.n * g.oh * g.ow;
+    CN_CHECK_ARG(pixels < 0x7fffffffL, "cn_dwconv3x3_wgrad: tensor too large");       // (so the plan's per_slice fits the kernel's int)
+    const ChanSlicesPlan p = chan_slices_plan(pixels, g.c / V, DW_WGRAD_MIN_ROWS);
     CN_CHECK_ARG(slices == p.slices, "cn_dwconv3x3_wgrad: %d slices given, the plan has %d (cn_dwconv3x3_wgrad_slices)", slices, p.slices);
-    hipLaunchKernelGGL((dwconv3x3_wgrad_kernel<S, V>), dim3(p.cb, p.slices), dim3(256), 0, s, x, gy, part, h, wd, c, oh, ow, ph, pw,
-                       (int)pixels, p.per_slice, p.TX, p.TY);
+    hipLaunchKernelGGL((dwconv3x3_wgrad_kernel<S, V>), dim3(p.cb, p.slices), dim3(256), 0, s, x, gy, part, g.h, g.wd, g.c, g.oh, g.ow, g.ph,
+                       g.pw, (int)pixels, (int)p.per_slice, p.TX, p.TY);
     CN_LAUNCH_CHECK();
     return CN_OK;
 }
@@ -379,10 +340,11 @@ extern "C" int cn_dwconv3x3_fwd(const float* x, const float* w, const float* bia
     CN_CHECK_ARG(n > 0 && h > 0 && wd > 0 && c > 0, "cn_dwconv3x3_fwd: bad extents n %d h %d w %d c %d", n, h, wd, c);
     CN_CHECK_ARG(stride == 1 || stride == 2, "cn_dwconv3x3_fwd: stride must be 1 or 2 (got %d)", stride);
     hipStream_t s = (hipStream_t)stream;
-    const bool v4 = c % 4 == 0 && ((uintptr_t)x | (uintptr_t)w | (uintptr_t)y | (uintptr_t)bias) % 16 == 0;
-    if (stride == 1)
-        return v4 ? launch_dw<1, 4, 4, 2>(x, w, bias, y, n, h, wd, c, act, slope, s) : launch_dw<1, 1, 4, 2>(x, w, bias, y, n, h, wd, c, act, slope, s);
-    return v4 ? launch_dw<2, 4, 2, 2>(x, w, bias, y, n, h, wd, c, act, slope, s) : launch_dw<2, 1, 2, 2>(x, w, bias, y, n, h, wd, c, act, slope, s);
+    const DwGeom g = dw_geom(n, h, wd, c, stride);
+    // operands that are not 16-byte aligned take the scalar walk (a NULL bias counts as aligned); 4 x 2 outputs per lane at stride 1, 2 x 2 at 2
+    return dw_instance(stride, c % 4 == 0 && aligned16(x, w, y, bias), [&](auto S, auto V) {
+        return launch_dw<S.value, V.value, S.value == 1 ? 4 : 2, 2>(g, x, w, bias, y, act, slope, s);
+    });
 }
 
 extern "C" int cn_dwconv3x3_dgrad(const float* gy, const float* w, float* gx, int n, int h, int wd, int c, int stride, void* stream) {
@@ -390,15 +352,16 @@ extern "C" int cn_dwconv3x3_dgrad(const float* gy, const float* w, float* gx, in
     CN_CHECK_ARG(n > 0 && h > 0 && wd > 0 && c > 0, "cn_dwconv3x3_dgrad: bad extents n %d h %d w %d c %d", n, h, wd, c);
     CN_CHECK_ARG(stride == 1 || stride == 2, "cn_dwconv3x3_dgrad: stride must be 1 or 2 (got %d)", stride);
     hipStream_t s = (hipStream_t)stream;
-    const bool v4 = c % 4 == 0 && ((uintptr_t)gy | (uintptr_t)w | (uintptr_t)gx) % 16 == 0;
-    if (stride == 1) return v4 ? launch_dw_dgrad<1, 4, 4, 2>(gy, w, gx, n, h, wd, c, s) : launch_dw_dgrad<1, 1, 4, 2>(gy, w, gx, n, h, wd, c, s);
-    return v4 ? launch_dw_dgrad<2, 4, 4, 2>(gy, w, gx, n, h, wd, c, s) : launch_dw_dgrad<2, 1, 4, 2>(gy, w, gx, n, h, wd, c, s);
+    const DwGeom g = dw_geom(n, h, wd, c, stride);
+    return dw_instance(stride, c % 4 == 0 && aligned16(gy, w, gx), [&](auto S, auto V) {      // (misaligned: the scalar walk, as the forward)
+        return launch_dw_dgrad<S.value, V.value, 4, 2>(g, gy, w, gx, s);
+    });
 }
 
 extern "C" int cn_dwconv3x3_wgrad_slices(int n, int h, int wd, int c, int stride) {
     CN_CHECK_ARG(n > 0 && h > 0 && wd > 0 && c > 0 && (stride == 1 || stride == 2), "cn_dwconv3x3_wgrad_slices: bad extents");
-    const long pixels = (long)n * ((h + stride - 1) / stride) * ((wd + stride - 1) / stride);
-    return dw_wgrad_plan(pixels, c % 4 == 0 ? c / 4 : c).slices;
+    const DwGeom g = dw_geom(n, h, wd, c, stride);
+    return chan_slices_plan((long)n * g.oh * g.ow, c % 4 == 0 ? c / 4 : c, DW_WGRAD_MIN_ROWS).slices;
 }
 
 extern "C" int cn_dwconv3x3_wgrad(const float* x, const float* gy, float* part, int slices, int n, int h, int wd, int c, int stride,
@@ -407,11 +370,11 @@ extern "C" int cn_dwconv3x3_wgrad(const float* x, const float* gy, float* part, 
     CN_CHECK_ARG(n > 0 && h > 0 && wd > 0 && c > 0, "cn_dwconv3x3_wgrad: bad extents n %d h %d w %d c %d", n, h, wd, c);
     CN_CHECK_ARG(stride == 1 || stride == 2, "cn_dwconv3x3_wgrad: stride must be 1 or 2 (got %d)", stride);
     hipStream_t s = (hipStream_t)stream;
-    if (c % 4 == 0) {                                  // (the slice plan follows c alone, so the float4 walk is not optional here)
-        CN_CHECK_ARG(((uintptr_t)x | (uintptr_t)gy) % 16 == 0, "cn_dwconv3x3_wgrad: x and gy must be 16-byte aligned when c %% 4 == 0");
-        return stride == 1 ? launch_dw_wgrad<1, 4>(x, gy, part, slices, n, h, wd, c, s) : launch_dw_wgrad<2, 4>(x, gy, part, slices, n, h, wd, c, s);
-    }
-    return stride == 1 ? launch_dw_wgrad<1, 1>(x, gy, part, slices, n, h, wd, c, s) : launch_dw_wgrad<2, 1>(x, gy, part, slices, n, h, wd, c, s);
+    // Unlike the forward and the input gradient, misaligned operands are refused, not walked as scalars: the slice plan -- and with it
+    // the count the caller sized `part` by, cn_dwconv3x3_wgrad_slices -- follows c alone, so the float4 walk is not optional here.
+    CN_CHECK_ARG(c % 4 != 0 || aligned16(x, gy), "cn_dwconv3x3_wgrad: x and gy must be 16-byte aligned when c %% 4 == 0");
+    const DwGeom g = dw_geom(n, h, wd, c, stride);
+    return dw_instance(stride, c % 4 == 0, [&](auto S, auto V) { return launch_dw_wgrad<S.value, V.value>(g, x, gy, part, slices, s); });
 }
 
 extern "C" int cn_image_preprocess(const void* x, int x_dt, float* y, int n, int h, int wd, int c, int oh, int ow, float in_mul,

@@ -1381,6 +1381,17 @@ def dwconv3x3_dgrad(gy, w, in_shape, stride, out=None):
     return gx
 
 
+def _slice_partials(query, dims, cols, device, name, launch):
+    """The per-slice partials (slices, cols) of a per-channel training reduction: slices = query(*dims), the library's own count;
+    launch(part pointer, slices) is the checked call `name` that fills them."""
+    slices = query(*dims)
+    if slices <= 0:
+        check(slices, query.__name__)
+    part = torch.empty((slices, cols), device=device, dtype=torch.float32)
+    check(launch(_fptr(part), slices), name)
+    return part
+
+
 def dwconv3x3_wgrad(x, gy, stride, out=None, accumulate=True, defer=True):
     """Filter gradient (3, 3, c, 1) of dwconv3x3_fwd.  cn_dwconv3x3_wgrad leaves one partial filter per slice of output pixels
     (the library's plan: cn_dwconv3x3_wgrad_slices) and sum_rows_into adds the slices in slice order -- as every per-channel
@@ -1390,11 +1401,8 @@ def dwconv3x3_wgrad(x, gy, stride, out=None, accumulate=True, defer=True):
     x, gy = _c(f32(x)), _c(f32(gy))
     n, h, wd, c = x.shape
     assert tuple(gy.shape) == (n, -(-h // stride), -(-wd // stride), c), (tuple(gy.shape), tuple(x.shape), stride)
-    slices = lib.cn_dwconv3x3_wgrad_slices(n, h, wd, c, stride)
-    if slices <= 0:
-        check(slices, "cn_dwconv3x3_wgrad_slices")
-    part = torch.empty((slices, 9 * c), device=x.device, dtype=torch.float32)
-    check(lib.cn_dwconv3x3_wgrad(_ptr(x), _ptr(gy), _fptr(part), slices, n, h, wd, c, stride, _stream()), "cn_dwconv3x3_wgrad")
+    part = _slice_partials(lib.cn_dwconv3x3_wgrad_slices, (n, h, wd, c, stride), 9 * c, x.device, "cn_dwconv3x3_wgrad",
+                           lambda p, slices: lib.cn_dwconv3x3_wgrad(_ptr(x), _ptr(gy), p, slices, n, h, wd, c, stride, _stream()))
     if out is None:
         out, accumulate = torch.empty((3, 3, c, 1), device=x.device, dtype=torch.float32), False
     assert out.is_contiguous() and out.numel() == 9 * c and out.dtype == torch.float32
@@ -1438,15 +1446,13 @@ def bn_train_bwd(gy, y, x, saved, act=ACT_NONE):
     m = x.numel() // c
     if BRANCH_LOG is not None and act == ACT_RELU6:
         BRANCH_LOG.append(("relu6", ((y.detach() > 0) & (y.detach() < 6)).reshape(-1).cpu()))
-    slices = lib.cn_bn_train_bwd_slices(m, c)
-    if slices <= 0:
-        check(slices, "cn_bn_train_bwd_slices")
-    part = torch.empty((slices, 2 * c), device=x.device, dtype=torch.float32)
     yp = _fptr(y) if act == ACT_RELU6 else None
-    check(lib.cn_bn_train_bwd_reduce(_fptr(gy), yp, _fptr(x), _fptr(mean), _fptr(r), _fptr(part), slices, m, c, act, _stream()),
-          "cn_bn_train_bwd_reduce")
+    part = _slice_partials(lib.cn_bn_train_bwd_slices, (m, c), 2 * c, x.device, "cn_bn_train_bwd_reduce",
+                           lambda p, slices: lib.cn_bn_train_bwd_reduce(_fptr(gy), yp, _fptr(x), _fptr(mean), _fptr(r), p, slices, m, c, act, _stream()))
     sums = torch.empty(2 * c, device=x.device, dtype=torch.float32)
-    check(lib.cn_sum_rows_into(_fptr(part), _fptr(sums), slices, 2 * c, 0, _stream()), "cn_sum_rows_into")
+    # not sum_rows_into(..., accumulate=False, defer=False): the same one call, but under a grad_sink it also books this stream as one the
+    # sink launched on -- with frozen kernels (only gamma / beta trained) no sink launch is on it, and the join would newly wait on it
+    check(lib.cn_sum_rows_into(_fptr(part), _fptr(sums), part.shape[0], 2 * c, 0, _stream()), "cn_sum_rows_into")
     gx = torch.empty_like(x)
     check(lib.cn_bn_train_bwd_apply(_fptr(gy), yp, _fptr(x), _fptr(mean), _fptr(r), _fptr(a), _fptr(sums), _fptr(gx), m, c, act,
                                     _stream()), "cn_bn_train_bwd_apply")

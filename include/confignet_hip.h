@@ -515,6 +515,11 @@ int cn_bn_train_coef(const float* s1, const float* s2, const float* gamma, const
                      double momentum, int bessel, void* stream);
 int cn_bn_train_apply(const float* x, const float* a, const float* b, float* y, long long m, int c, int act, void* stream);
 int cn_bn_train_bwd_slices(long long m, int c);
+/* Diagnostic: the slice rule of the two per-channel training reductions (cn_dwconv3x3_wgrad: rows = n oh ow output pixels,
+ * min_rows = 64; cn_bn_train_bwd_reduce: rows = m, min_rows = 0), decided by the function the calls decide with, without a device.
+ * out = {TX channel groups x TY row lanes of a workgroup (4 channels per group where c % 4 == 0, else 1), channel blocks, slices,
+ * rows per slice}; the grid is (channel blocks, slices). */
+int cn_chan_slices_plan(long long rows, int c, int min_rows, int out[5]);
 int cn_bn_train_bwd_reduce(const float* gy, const float* y, const float* x, const float* mean, const float* r, float* part, int slices,
                            long long m, int c, int act, void* stream);
 int cn_bn_train_bwd_apply(const float* gy, const float* y, const float* x, const float* mean, const float* r, const float* a,

@@ -1,37 +1,25 @@
 """The three BatchNormalization training kernels whose arithmetic can be made exact (csrc/bn_train.hip: bn_train_apply_kernel,
 bn_train_bwd_reduce_kernel, bn_train_bwd_apply_kernel), called through `lib` on edge shapes: dead lanes in the last channel
-block, the scalar path (c % 4 != 0), one slice, several slices with a ragged last one.  (cn_bn_train_coef takes a reciprocal
-root and has no exact form: tests/test_bn_train_gpu.py holds it against float64.)
+block, the scalar path (c % 4 != 0; with c = 70 over two channel blocks, the second with 6 live lanes of 64), one slice,
+several slices with a ragged last one.  (cn_bn_train_coef takes a reciprocal root and has no exact form:
+tests/test_bn_train_gpu.py holds it against float64.)
 
 Exact arithmetic: x, gy, y, mean, a, b are integers of at most 9 in size, r is 1/2, the sums handed to the backward apply pass
 are multiples of m and m is a power of two there, so every intermediate is a multiple of 1/4 far below 2^24 and fp32 holds it
 exactly, fused or not, in any order: results are compared with the float64 statement by torch.equal.  y takes the values 0 and 6
-themselves (the mask 0 < y < 6 excludes both).  Outputs hold NaN before the call; 256 guard floats on both sides stay."""
-import numpy as np
+themselves (the mask 0 < y < 6 excludes both).  Outputs hold NaN before the call; 256 guard floats on both sides stay
+(tests/chan_slices_cases.py: Guarded)."""
 import pytest
 import torch
 
+from tests.chan_slices_cases import BN_REDUCE_SHAPES, Guarded, to_device as _dev
+
 pytestmark = pytest.mark.gpu
 
-GUARD, GUARD_VALUE = 256, 12345.0
 ACT_NONE, ACT_RELU6 = 0, 4
-REDUCE_SHAPES = [(60, 8), (37, 6), (512, 96), (1000, 260), (16, 1280)]       # (rows, channels)
-APPLY_SHAPES = [(64, 8), (32, 6), (512, 96), (1024, 260), (16, 1280)]        # rows a power of two: 1 / m is exact
+REDUCE_SHAPES = BN_REDUCE_SHAPES                                                      # (rows, channels)
+APPLY_SHAPES = [(64, 8), (32, 6), (512, 96), (1024, 260), (16, 1280), (32, 70)]       # rows a power of two: 1 / m is exact
 _id = lambda s: "x".join(map(str, s))
-
-
-class Guarded:
-    def __init__(self, shape):
-        k = int(np.prod(shape))
-        self.buf = torch.full((k + 2 * GUARD,), GUARD_VALUE, device="cuda", dtype=torch.float32)
-        self.t = self.buf[GUARD:GUARD + k].view(shape)
-        self.t.fill_(float("nan"))
-
-    def check(self, want, what):
-        edge = torch.full((GUARD,), GUARD_VALUE, device="cuda")
-        assert torch.equal(self.buf[:GUARD], edge) and torch.equal(self.buf[-GUARD:], edge), what + ": a guard was written"
-        got = self.t.double().cpu()
-        assert torch.equal(got, want.reshape(got.shape)), "%s: %d of %d elements wrong" % (what, int((got != want.reshape(got.shape)).sum()), got.numel())
 
 
 def _case(m, c, seed):
@@ -43,10 +31,6 @@ def _case(m, c, seed):
 
 def _g(t, act):
     return t["gy"] * ((t["y"] > 0) & (t["y"] < 6)).double() if act == ACT_RELU6 else t["gy"]
-
-
-def _dev(t):
-    return t.float().cuda().contiguous()
 
 
 def _stream():

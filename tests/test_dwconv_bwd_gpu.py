@@ -9,21 +9,23 @@ smallest shapes at which each index rule can go wrong, at both strides:
   (2, 33, 17, 8)   more pixels than one filter-gradient slice: 3 slices at stride 1
   (2, 33, 33, 8)   the smallest such shape with two slices at STRIDE 2 (578 output pixels; a slice at c = 8 holds 512 -- at
                    stride 2 (2, 33, 17, 8) has 306 and stays one slice)
+  (1, 5, 5, 70)    c % 4 != 0 with c > 64: the scalar path with two channel blocks, the last one with 58 dead lanes of 64
 
 Exact arithmetic: inputs and taps are integers in [-4, 4], so every term is at most 16 in size and the longest reduction
 (2 * 33 * 33 terms) stays far below 2^24: fp32 holds every sum exactly in any order, and each result is compared with the float64
-statement by torch.equal.  What a call must write holds NaN before it; 256 guard floats on both sides must be unchanged."""
+statement by torch.equal.  What a call must write holds NaN before it; 256 guard floats on both sides must be unchanged
+(tests/chan_slices_cases.py: Guarded; the shapes live there too, next to the recorded slice plans that cover them)."""
 import functools
 
 import numpy as np
 import pytest
 import torch
 
+from tests.chan_slices_cases import DW_EDGE_SHAPES, NAN, Guarded, to_device as _dev
+
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(1, 1, 1, 4), (2, 5, 7, 8), (3, 8, 6, 6), (1, 9, 9, 32), (2, 4, 4, 960), (2, 33, 17, 8), (2, 33, 33, 8)]
-GUARD, GUARD_VALUE = 256, 12345.0
-NAN = float("nan")
+SHAPES = DW_EDGE_SHAPES
 _id = lambda s: "x".join(map(str, s))
 
 
@@ -65,32 +67,6 @@ def _case(shape, stride):
     oh, ow = _geom(h, stride)[0], _geom(wd, stride)[0]
     x, w, gy = _ints(shape, 11 * h + wd + c + stride), _ints((3, 3, c), c + 5), _ints((n, oh, ow, c), 3 * h + 7 * wd + c + stride)
     return (x, w, gy) + _statement(x, w, gy, stride)
-
-
-class Guarded:
-    """a contiguous fp32 tensor of `shape` inside a larger allocation with sentinels on both sides, holding `fill`"""
-
-    def __init__(self, shape, fill):
-        k = int(np.prod(shape))
-        self.buf = torch.full((k + 2 * GUARD,), GUARD_VALUE, device="cuda", dtype=torch.float32)
-        self.t = self.buf[GUARD:GUARD + k].view(shape)
-        if isinstance(fill, float):
-            self.t.fill_(fill)
-        else:
-            self.t.copy_(fill)
-
-    def check(self, want, what):
-        edge = torch.full((GUARD,), GUARD_VALUE, device="cuda")
-        assert torch.equal(self.buf[:GUARD], edge) and torch.equal(self.buf[-GUARD:], edge), what + ": a guard was written"
-        got, want = self.t.double().cpu(), torch.from_numpy(np.ascontiguousarray(want)).reshape(self.t.shape)
-        if not torch.equal(got, want):
-            bad = (got != want).nonzero()
-            i = tuple(bad[0].tolist())
-            raise AssertionError("%s: %d of %d elements wrong, first at %s: got %r, want %r" % (what, len(bad), got.numel(), i, float(got[i]), float(want[i])))
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).float().cuda()
 
 
 @pytest.mark.parametrize("stride", [1, 2])
