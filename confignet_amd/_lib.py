@@ -156,6 +156,7 @@ SIGNATURES = {
     "cn_euler_matrix_bwd": [_p, _p, _p, _i, _p],
     "cn_rotate3d_fwd": [_p, _p, _p, _i, _i, _i, _p],
     "cn_rotate3d_bwd": [_p, _p, _p, _p, _p, _i, _i, _i, _p],
+    "cn_rotate3d_bwd_plan": [_i, _i, _i, _i, ctypes.POINTER(ctypes.c_int * 4)],
     "cn_adam_step": [_p, _p, _p, _p, _p, _z, _p, _f, _f, _f, _f, _p],
     "cn_ema_step": [_p, _p, _z, _f, _p],
     "cn_gather_images_u8": [_p, _p, _p, _p, _i, _i, _i, _i, _p],

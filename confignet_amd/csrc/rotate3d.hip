@@ -362,36 +362,61 @@ extern "C" int cn_rotate3d_fwd(const float* grid, const float* rot, float* out, 
     return CN_OK;
 }
 
-extern "C" int cn_rotate3d_bwd(const float* grid, const float* rot, const float* gout, float* ggrid, float* grot, int n,
-                               int g, int c, void* stream) {
-    CN_CHECK_ARG(grid && rot && gout && ggrid && n > 0 && g > 1 && c > 0 && c % 4 == 0, "rotate3d_bwd: bad args");
-    hipStream_t s = (hipStream_t)stream;
+// Which launch the backward pass gets: the one place that decides the path, the channels a workgroup owns and the grid
+// (cn_rotate3d_bwd launches it, cn_rotate3d_bwd_plan reports it).
+enum { ROT_BWD_DET = 0, ROT_BWD_LDS, ROT_BWD_GLOBAL };
+struct RotBwdPlan {
+    int path, cc, gx, gy;      // cc: channels per workgroup (the global-atomics kernel walks all c)
+};
+static RotBwdPlan plan_rotate3d_bwd(int n, int g, int c, bool det) {
     const long P = (long)g * g * g;
-    if (cn_det() && P * 8 <= SLAB_FLOATS) {
-        const int cblocks = cn_cdiv(c, 8);
-        float* parts = nullptr;
-        if (grot) {
-            parts = cn_det_ws(s, (size_t)cblocks * n * 9);
-            if (!parts) return CN_EINVAL;
-        }
-        hipLaunchKernelGGL(rotate3d_bwd_det_kernel, dim3(cblocks, n), dim3(64), 0, s, grid, rot, gout, ggrid, parts, g, c);
-        CN_LAUNCH_CHECK();
-        if (grot) return cn_sum_parts(parts, grot, cblocks, (long)n * 9, 0, 1.f, s);
-        return CN_OK;
-    }
-    if (grot) {
-        if (int ez__ = cn_zero_async(grot, sizeof(float) * n * 9, s)) return ez__;
-    }
+    if (det && P * 8 <= SLAB_FLOATS) return {ROT_BWD_DET, 8, cn_cdiv(c, 8), n};
     if (P * 4 <= SLAB_FLOATS) {
         int CC = (int)(SLAB_FLOATS / P);
         if (CC > c) CC = c;
         CC = CC / 4 * 4;
         // fewer channels per workgroup while that still adds workgroups on idle CUs (n = 8, C = 128: 128 -> 256 workgroups)
         while (CC > 4 && (long)cn_cdiv(c, CC) * n < 256) CC -= 4;
-        hipLaunchKernelGGL(rotate3d_bwd_lds_kernel, dim3(cn_cdiv(c, CC), n), dim3(256), 0, s, grid, rot, gout, ggrid, grot, g, c, CC);
+        return {ROT_BWD_LDS, CC, cn_cdiv(c, CC), n};
+    }
+    return {ROT_BWD_GLOBAL, c, cn_cdiv(P, 256), n};
+}
+
+#define ROT_BWD_ARGS_OK(n, g, c) ((n) > 0 && (g) > 1 && (c) > 0 && (c) % 4 == 0)
+
+extern "C" int cn_rotate3d_bwd_plan(int n, int g, int c, int det, int out[4]) {
+    CN_CHECK_ARG(out && ROT_BWD_ARGS_OK(n, g, c), "rotate3d_bwd_plan: bad args");
+    const RotBwdPlan p = plan_rotate3d_bwd(n, g, c, det != 0);
+    out[0] = p.path; out[1] = p.cc; out[2] = p.gx; out[3] = p.gy;
+    return CN_OK;
+}
+
+extern "C" int cn_rotate3d_bwd(const float* grid, const float* rot, const float* gout, float* ggrid, float* grot, int n,
+                               int g, int c, void* stream) {
+    CN_CHECK_ARG(grid && rot && gout && ggrid && ROT_BWD_ARGS_OK(n, g, c), "rotate3d_bwd: bad args");
+    hipStream_t s = (hipStream_t)stream;
+    const long P = (long)g * g * g;
+    const RotBwdPlan p = plan_rotate3d_bwd(n, g, c, cn_det() != 0);
+    const dim3 blocks(p.gx, p.gy);
+    if (p.path == ROT_BWD_DET) {
+        float* parts = nullptr;
+        if (grot) {
+            parts = cn_det_ws(s, (size_t)p.gx * n * 9);
+            if (!parts) return CN_EINVAL;
+        }
+        hipLaunchKernelGGL(rotate3d_bwd_det_kernel, blocks, dim3(64), 0, s, grid, rot, gout, ggrid, parts, g, c);
+        CN_LAUNCH_CHECK();
+        if (grot) return cn_sum_parts(parts, grot, p.gx, (long)n * 9, 0, 1.f, s);
+        return CN_OK;
+    }
+    if (grot) {
+        if (int ez__ = cn_zero_async(grot, sizeof(float) * n * 9, s)) return ez__;
+    }
+    if (p.path == ROT_BWD_LDS) {
+        hipLaunchKernelGGL(rotate3d_bwd_lds_kernel, blocks, dim3(256), 0, s, grid, rot, gout, ggrid, grot, g, c, p.cc);
     } else {
         if (int ez__ = cn_zero_async(ggrid, sizeof(float) * n * P * c, s)) return ez__;
-        hipLaunchKernelGGL(rotate3d_bwd_kernel, dim3(cn_cdiv(P, 256), n), dim3(256), 0, s, grid, rot, gout, ggrid, grot, g, c / 4);
+        hipLaunchKernelGGL(rotate3d_bwd_kernel, blocks, dim3(256), 0, s, grid, rot, gout, ggrid, grot, g, c / 4);
     }
     CN_LAUNCH_CHECK();
     return CN_OK;

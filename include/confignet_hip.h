@@ -542,6 +542,10 @@ int cn_rotate3d_fwd(const float* grid, const float* rot /* (N,3,3) */, float* ou
 /* ggrid (overwritten) and grot (N,3,3) (overwritten; through `diffs` only, l.105) */
 int cn_rotate3d_bwd(const float* grid, const float* rot, const float* gout, float* ggrid, float* grot,
                     int n, int g, int c, void* stream);
+/* Diagnostic: the launch cn_rotate3d_bwd gives a shape, decided by the function the call decides with, without a device
+ * (det: the deterministic mode as an argument).  out = {path (0 deterministic wave, 1 LDS slab, 2 global atomics), channels per
+ * workgroup, grid x, grid y}; refuses the shapes the call refuses. */
+int cn_rotate3d_bwd_plan(int n, int g, int c, int det, int out[4]);
 
 /* ---- optimizer: Keras Adam + EMA in one pass (confignet_first_stage.py:393-400,601-602) -----
  * theta -= lr_t * m/(sqrt(v)+eps); lr_t = lr*sqrt(1-b2^t)/(1-b1^t) is computed by the host (shared step

@@ -350,7 +350,7 @@ def euler_angles_to_matrix(angles):
 def transform_3d_grid(grid, transform):
     """transform_3d_grid_tf (confignet_utils.py:63-120): rigid rotation about the grid
     centre, clamp-to-edge, trilinear (x, then y, then z).  tf.floor has zero gradient;
-    tf.clip_by_value passes gradient strictly inside the interval (R12)."""
+    tf.clip_by_value passes gradient on the closed interval, ends included, as torch.clamp does (R12)."""
     n, g = grid.shape[0], grid.shape[1]
     assert grid.shape[1] == grid.shape[2] == grid.shape[3]
     centre = (g - 1) / 2
@@ -358,7 +358,7 @@ def transform_3d_grid(grid, transform):
     xs, ys, zs = torch.meshgrid(ar, ar, ar, indexing="ij")
     coords = torch.stack([xs.reshape(-1), ys.reshape(-1), zs.reshape(-1)])      # (3, P)
     tc = transform.to(grid.dtype) @ (coords - centre) + centre                  # (N, 3, P)
-    # clip_by_value: gradient 1 strictly inside, 0 outside/at the clamp
+    # clip_by_value: gradient 1 on [0, g - 1], both ends included, 0 outside
     tc = torch.clamp(tc, 0, g - 1)
     fl = torch.clamp(torch.floor(tc.detach()), 0, g - 1)
     ce = torch.clamp(fl + 1, 0, g - 1)
