@@ -133,6 +133,9 @@ SIGNATURES = {
     "cn_row_scale_diff": [_p, _p, _p, _p, _i, ctypes.c_size_t, _f, _i, _p],
     "cn_tap_bwd": [_p, _p, _p, _p, _p, _i, ctypes.c_size_t, _f, _i, _f, _i, _p],
     "cn_maxpool2_bwd_act": [_p, _p, _p, _p, _f, _p, _i, _i, _i, _i, _i, _i, _p],
+    "cn_stream_plan": [_i, _i, ctypes.c_longlong, _z, _i, _i, _i, _i, _i, _i, ctypes.c_uint, _i, ctypes.POINTER(ctypes.c_longlong * 4)],
+    "cn_stream_plan_ptrs": [_i, _i, _i, ctypes.c_longlong, _z, _i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_void_p * 4), _i, ctypes.POINTER(ctypes.c_longlong * 4)],
+    "cn_stream_last_plan": [ctypes.POINTER(ctypes.c_longlong * 5)],
     "cn_masked_diff": [_p, _p, _p, _p, _z, _i, _p],
     "cn_maxpool_fwd": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "cn_maxpool_bwd": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],

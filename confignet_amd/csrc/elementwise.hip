@@ -1011,6 +1011,101 @@ inline int ew_blocks(size_t n) {
     return (int)(b > 8192 ? 8192 : (b ? b : 1));
 }
 
+// ---- the launch rule of the streaming maps, row maps, loss reductions and pools: ONE pure host function.  Every entry below builds
+// its request (sizes, and a bit per operand that is aligned for 4-wide access, in the entry's argument order; a NULL optional operand
+// counts as aligned), asks plan_stream and launches what it says; cn_stream_plan reports the same answer without a device. ----
+enum StreamOp {
+    SP_ACT_FWD, SP_ACT_BWD, SP_AXPBY, SP_MUL, SP_CAST, SP_SQDIFF_SUM, SP_ROW_SUMSQ, SP_ROW_SCALE, SP_ROW_SCALE_DIFF, SP_TAP_BWD,
+    SP_MAXPOOL_FWD, SP_AVGPOOL3_SAME, SP_MAXPOOL_BWD, SP_MAXPOOL2_BWD_ACT, SP_OPS
+};
+enum StreamPath { SP_SCALAR = 0, SP_VEC = 1, SP_POOL2 = 2 };       // one element per lane / 4 per lane (4-channel groups) / the 2 x 2 window kernel
+struct StreamReq {
+    int op, dt;
+    long rows;             // rows of a row map, samples of a pool; 1 otherwise
+    size_t row;            // row length; numel of a flat map or reduction
+    int c, h, w, k, s, pad;
+    unsigned aligned;
+    int det;
+};
+struct StreamPlan {
+    int path, gx, gy;
+    long parts;            // floats of deterministic partials (0: none)
+    int oh, ow;            // pools
+};
+// aligned operands an entry looks at
+constexpr int SP_OPERANDS[SP_OPS] = {2, 3, 3, 3, 2, 2, 1, 2, 3, 4, 2, 2, 3, 4};
+
+inline int plan_stream(const StreamReq& r, StreamPlan* p) {
+    const unsigned all = (1u << SP_OPERANDS[r.op]) - 1u;
+    const bool al = (r.aligned & all) == all;
+    *p = StreamPlan{SP_SCALAR, 1, 1, 0, 0, 0};
+    switch (r.op) {
+        case SP_ACT_FWD: case SP_ACT_BWD: case SP_AXPBY: case SP_MUL: case SP_CAST:
+            p->path = al ? SP_VEC : SP_SCALAR;
+            p->gx = ew_blocks(al ? (r.row + 3) / 4 : r.row);      // quarter the grid: four elements per lane per trip
+            return CN_OK;
+        case SP_SQDIFF_SUM: {
+            const int vec = al;
+            p->path = vec ? SP_VEC : SP_SCALAR;
+            p->gx = ew_blocks(r.row / (vec ? 4 : 1) + 1) > 512 ? 512 : ew_blocks(r.row / (vec ? 4 : 1) + 1);   // one atomic each
+            p->parts = r.det ? p->gx : 0;
+            return CN_OK;
+        }
+        case SP_ROW_SUMSQ: {
+            int bpr = (int)((r.row + 256 * 32 - 1) / (256 * 32));
+            if (bpr > 64) bpr = 64;
+            p->path = al && r.row % 4 == 0 ? SP_VEC : SP_SCALAR;
+            p->gx = bpr; p->gy = (int)r.rows;
+            p->parts = r.det ? (long)bpr * r.rows : 0;
+            return CN_OK;
+        }
+        case SP_ROW_SCALE: case SP_ROW_SCALE_DIFF: case SP_TAP_BWD: {
+            int bpr = (int)((r.row + 256 * 16 - 1) / (256 * 16));
+            if (bpr > 512) bpr = 512;
+            p->path = al && r.row % 4 == 0 ? SP_VEC : SP_SCALAR;
+            p->gx = bpr; p->gy = (int)r.rows;
+            return CN_OK;
+        }
+        case SP_MAXPOOL_FWD: {
+            const int n = (int)r.rows, oh = (r.h + 2 * r.pad - r.k) / r.s + 1, ow = (r.w + 2 * r.pad - r.k) / r.s + 1;
+            const size_t total = (size_t)n * oh * ow * r.c;
+            p->oh = oh; p->ow = ow;
+            if (r.c % 4 == 0 && al && total / 4 < (1UL << 30) && (size_t)n * r.h * r.w * r.c / 4 < (1UL << 30)) {    // 32-bit indices
+                p->path = SP_VEC; p->gx = ew_blocks(total / 4);
+            } else {
+                p->path = SP_SCALAR; p->gx = ew_blocks(total);
+            }
+            return CN_OK;
+        }
+        case SP_AVGPOOL3_SAME: {
+            const bool v4 = r.c % 4 == 0 && al;
+            p->path = v4 ? SP_VEC : SP_SCALAR;
+            p->gx = ew_blocks((size_t)r.rows * r.h * r.w * (v4 ? r.c / 4 : r.c));
+            return CN_OK;
+        }
+        case SP_MAXPOOL_BWD: {
+            const int n = (int)r.rows, oh = (r.h + 2 * r.pad - r.k) / r.s + 1, ow = (r.w + 2 * r.pad - r.k) / r.s + 1;
+            const size_t total = (size_t)n * r.h * r.w * r.c;
+            p->oh = oh; p->ow = ow;
+            if (r.k == 2 && r.s == 2 && r.pad == 0 && r.h % 2 == 0 && r.w % 2 == 0 && r.c % 4 == 0 && al) {
+                p->path = SP_POOL2; p->gx = ew_blocks((size_t)((long)n * oh * ow * (r.c / 4)));
+            } else if (r.c % 4 == 0 && al && total / 4 < 2147483647UL) {                                             // 32-bit indices
+                p->path = SP_VEC; p->gx = ew_blocks(total / 4);
+            } else {
+                p->path = SP_SCALAR; p->gx = ew_blocks(total);
+            }
+            return CN_OK;
+        }
+        case SP_MAXPOOL2_BWD_ACT:
+            if (r.h % 2 || r.w % 2 || r.c % 4 || !al) return CN_EUNSUPPORTED;
+            p->path = SP_POOL2; p->oh = r.h / 2; p->ow = r.w / 2;
+            p->gx = ew_blocks((size_t)((long)r.rows * p->oh * p->ow * (r.c / 4)));
+            return CN_OK;
+        default: break;
+    }
+    return CN_EINVAL;
+}
+
 }  // namespace
 
 // ---- the launch of an (n, s, c) -> (n, c) reduction: decided here, performed by nc_reduce_run ("Statistics dispatch") ----
@@ -1265,15 +1360,41 @@ extern "C" int cn_norm_apply(int mode, int dir, const void* x1, const void* x2, 
     CN_LAUNCH_CHECK();                                                                                         \
     return CN_OK;
 
-static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // 4-wide access of a tensor stored as `dt` needs 16-byte (fp32) / 8-byte (bf16) alignment (NULL counts as aligned)
 static inline bool alv(const void* p, int dt) { return ((uintptr_t)p & (dt == CN_BF16 ? 7 : 15)) == 0; }
-// 4-wide form of a streaming map when every pointer is aligned (quarter the grid: four elements per lane per trip)
-#define EW_LAUNCH_VT(kernel, n, vec, dt, ...)                                                                                    \
+// The `aligned` mask of an entry's operands: bit i = operand i (the entry's tensor operands in its argument order, SP_OPERANDS[op] of
+// them) may be accessed 4-wide as it is stored; a NULL optional operand counts as aligned (alv).  Operand 1 of a cast is stored as dst_dt.
+struct StreamPtrs { const void* p[4]; };
+static inline unsigned stream_mask(int op, int dt, int dst_dt, const StreamPtrs& o) {
+    unsigned m = 0;
+    for (int i = 0; i < SP_OPERANDS[op]; ++i)
+        if (alv(o.p[i], op == SP_CAST && i == 1 ? dst_dt : dt)) m |= 1u << i;
+    return m;
+}
+static inline StreamReq stream_req(int op, int dt, long rows, size_t row) {
+    return StreamReq{op, dt, rows, row, 0, 0, 0, 0, 0, 0, 0u, cn_det()};
+}
+static inline StreamReq pool_req(int op, int dt, int n, int h, int w, int c, int k, int s, int pad) {
+    return StreamReq{op, dt, n, 0, c, h, w, k, s, pad, 0u, cn_det()};
+}
+// what the last entry of this thread decided: {op, path, grid x, grid y, floats of partials}, op = -1 after a refusal or before any
+// call (cn_stream_last_plan: the tests read the decision of the call itself, not of a query beside it)
+static thread_local long long g_stream_last[5] = {-1, 0, 0, 0, 0};
+// every entry decides here: the mask of ITS pointers, then the plan
+static inline int stream_entry_plan(StreamReq r, int dst_dt, const StreamPtrs& o, StreamPlan* sp) {
+    r.aligned = stream_mask(r.op, r.dt, dst_dt, o);
+    const int e = plan_stream(r, sp);
+    g_stream_last[0] = e ? -1 : r.op; g_stream_last[1] = sp->path; g_stream_last[2] = sp->gx; g_stream_last[3] = sp->gy; g_stream_last[4] = sp->parts;
+    return e;
+}
+// a flat streaming map: its 4-wide form when the plan says so
+#define EW_LAUNCH_VT(kernel, op, n, ptrs, dt, ...)                                                                                \
     CN_CHECK_ARG((dt) == CN_F32 || (dt) == CN_BF16, "bad dtype code %d", (int)(dt));                                                \
+    StreamPlan sp;                                                                                                                \
+    if (int e__ = stream_entry_plan(stream_req(op, dt, 1, n), dt, ptrs, &sp)) return e__;                                         \
     CN_DISPATCH_DT(dt, {                                                                                                          \
-        if (vec) hipLaunchKernelGGL((kernel<true, T>), dim3(ew_blocks(((n) + 3) / 4)), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL((kernel<false, T>), dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__);             \
+        if (sp.path == SP_VEC) hipLaunchKernelGGL((kernel<true, T>), dim3(sp.gx), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); \
+        else hipLaunchKernelGGL((kernel<false, T>), dim3(sp.gx), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__);                  \
     });                                                                                                                           \
     CN_LAUNCH_CHECK();                                                                                                            \
     return CN_OK;
@@ -1281,29 +1402,31 @@ static inline bool alv(const void* p, int dt) { return ((uintptr_t)p & (dt == CN
 extern "C" int cn_act_fwd(const void* x, void* y, size_t numel, int act, float slope, int dt, void* stream) {
     CN_CHECK_ARG(x && y, "act_fwd: NULL");
     if (!numel) return CN_OK;
-    EW_LAUNCH_VT(act_fwd_kernel, numel, alv(x, dt) && alv(y, dt), dt, (const T*)x, (T*)y, numel, act, slope)
+    EW_LAUNCH_VT(act_fwd_kernel, SP_ACT_FWD, numel, (StreamPtrs{{x, y}}), dt, (const T*)x, (T*)y, numel, act, slope)
 }
 extern "C" int cn_act_bwd(const void* gy, const void* y, void* gx, size_t numel, int act, float slope, int dt, void* stream) {
     CN_CHECK_ARG(gy && y && gx, "act_bwd: NULL");
     if (!numel) return CN_OK;
-    EW_LAUNCH_VT(act_bwd_kernel, numel, alv(gy, dt) && alv(y, dt) && alv(gx, dt), dt, (const T*)gy, (const T*)y, (T*)gx, numel, act, slope)
+    EW_LAUNCH_VT(act_bwd_kernel, SP_ACT_BWD, numel, (StreamPtrs{{gy, y, gx}}), dt, (const T*)gy, (const T*)y, (T*)gx, numel, act, slope)
 }
 extern "C" int cn_axpby(const void* x, const void* y, void* out, size_t numel, float a, float b, int dt, void* stream) {
     CN_CHECK_ARG(x && out, "axpby: NULL");
     if (!numel) return CN_OK;
-    EW_LAUNCH_VT(axpby_kernel, numel, alv(x, dt) && alv(y, dt) && alv(out, dt), dt, (const T*)x, (const T*)y, (T*)out, numel, a, b)
+    EW_LAUNCH_VT(axpby_kernel, SP_AXPBY, numel, (StreamPtrs{{x, y, out}}), dt, (const T*)x, (const T*)y, (T*)out, numel, a, b)
 }
 extern "C" int cn_mul(const void* x, const void* y, void* out, size_t numel, int dt, void* stream) {
     CN_CHECK_ARG(x && y && out, "mul: NULL");
     if (!numel) return CN_OK;
-    EW_LAUNCH_VT(mul_kernel, numel, alv(x, dt) && alv(y, dt) && alv(out, dt), dt, (const T*)x, (const T*)y, (T*)out, numel)
+    EW_LAUNCH_VT(mul_kernel, SP_MUL, numel, (StreamPtrs{{x, y, out}}), dt, (const T*)x, (const T*)y, (T*)out, numel)
 }
 extern "C" int cn_cast(const void* src, int src_dt, void* dst, int dst_dt, size_t numel, void* stream) {
     CN_CHECK_ARG(src && dst && (src_dt == CN_F32 || src_dt == CN_BF16) && (dst_dt == CN_F32 || dst_dt == CN_BF16) && src_dt != dst_dt,
                  "cast: bad args");
     if (!numel) return CN_OK;
-    const int vec = alv(src, src_dt) && alv(dst, dst_dt);
-    const dim3 grid(ew_blocks(vec ? (numel + 3) / 4 : numel));
+    StreamPlan sp;
+    if (int e = stream_entry_plan(stream_req(SP_CAST, src_dt, 1, numel), dst_dt, StreamPtrs{{src, dst}}, &sp)) return e;
+    const int vec = sp.path == SP_VEC;
+    const dim3 grid(sp.gx);
     if (src_dt == CN_F32) hipLaunchKernelGGL((cast_kernel<float, bf16_t>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)src, (bf16_t*)dst, numel, vec);
     else hipLaunchKernelGGL((cast_kernel<bf16_t, float>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, (float*)dst, numel, vec);
     CN_LAUNCH_CHECK();
@@ -1312,11 +1435,12 @@ extern "C" int cn_cast(const void* src, int src_dt, void* dst, int dst_dt, size_
 extern "C" int cn_sqdiff_sum(const void* a, const void* b, float* out, size_t numel, float scale, int dt, void* stream) {
     CN_CHECK_ARG(a && b && out && (dt == CN_F32 || dt == CN_BF16), "sqdiff_sum: bad args");
     if (!numel) return CN_OK;
-    const int vec = alv(a, dt) && alv(b, dt);
-    const int blocks = ew_blocks(numel / (vec ? 4 : 1) + 1) > 512 ? 512 : ew_blocks(numel / (vec ? 4 : 1) + 1);   // one atomic each
+    StreamPlan sp;
+    if (int e = stream_entry_plan(stream_req(SP_SQDIFF_SUM, dt, 1, numel), dt, StreamPtrs{{a, b}}, &sp)) return e;
+    const int vec = sp.path == SP_VEC, blocks = sp.gx;
     float* parts = nullptr;
-    if (cn_det()) {
-        parts = cn_det_ws((hipStream_t)stream, (size_t)blocks);
+    if (sp.parts) {
+        parts = cn_det_ws((hipStream_t)stream, (size_t)sp.parts);
         if (!parts) return CN_EINVAL;
     }
     CN_DISPATCH_DT(dt, hipLaunchKernelGGL((sqdiff_sum_kernel<T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)a, (const T*)b, out, numel, scale, vec, parts));
@@ -1326,11 +1450,11 @@ extern "C" int cn_sqdiff_sum(const void* a, const void* b, float* out, size_t nu
 }
 extern "C" int cn_row_sumsq(const float* x, float* out, int n, size_t row, void* stream) {
     CN_CHECK_ARG(x && out && n > 0 && row > 0, "row_sumsq: bad args");
-    const int vec = al16(x) && row % 4 == 0;
-    int bpr = (int)((row + 256 * 32 - 1) / (256 * 32));
-    if (bpr > 64) bpr = 64;
-    if (cn_det()) {
-        float* parts = cn_det_ws((hipStream_t)stream, (size_t)bpr * n);
+    StreamPlan sp;
+    if (int e = stream_entry_plan(stream_req(SP_ROW_SUMSQ, CN_F32, n, row), CN_F32, StreamPtrs{{x}}, &sp)) return e;
+    const int vec = sp.path == SP_VEC, bpr = sp.gx;
+    if (sp.parts) {
+        float* parts = cn_det_ws((hipStream_t)stream, (size_t)sp.parts);
         if (!parts) return CN_EINVAL;
         hipLaunchKernelGGL(row_sumsq_kernel, dim3(bpr, n), dim3(256), 0, (hipStream_t)stream, x, out, row, vec, parts);
         CN_LAUNCH_CHECK();
@@ -1343,29 +1467,29 @@ extern "C" int cn_row_sumsq(const float* x, float* out, int n, size_t row, void*
 }
 extern "C" int cn_row_scale(const void* x, const float* s, void* out, int n, size_t row, float k, int dt, void* stream) {
     CN_CHECK_ARG(x && s && out && n > 0 && row > 0 && (dt == CN_F32 || dt == CN_BF16), "row_scale: bad args");
-    const int vec = alv(x, dt) && alv(out, dt) && row % 4 == 0;
-    int bpr = (int)((row + 256 * 16 - 1) / (256 * 16));
-    if (bpr > 512) bpr = 512;
-    CN_DISPATCH_DT(dt, hipLaunchKernelGGL((row_scale_kernel<T>), dim3(bpr, n), dim3(256), 0, (hipStream_t)stream, (const T*)x, s, (T*)out, row, k, vec));
+    StreamPlan sp;
+    if (int e = stream_entry_plan(stream_req(SP_ROW_SCALE, dt, n, row), dt, StreamPtrs{{x, out}}, &sp)) return e;
+    const int vec = sp.path == SP_VEC;
+    CN_DISPATCH_DT(dt, hipLaunchKernelGGL((row_scale_kernel<T>), dim3(sp.gx, sp.gy), dim3(256), 0, (hipStream_t)stream, (const T*)x, s, (T*)out, row, k, vec));
     CN_LAUNCH_CHECK();
     return CN_OK;
 }
 extern "C" int cn_row_scale_diff(const void* x, const void* x2, const float* s, void* out, int n, size_t row, float k, int dt, void* stream) {
     CN_CHECK_ARG(x && x2 && s && out && n > 0 && row > 0 && (dt == CN_F32 || dt == CN_BF16), "row_scale_diff: bad args");
-    const int vec = alv(x, dt) && alv(x2, dt) && alv(out, dt) && row % 4 == 0;
-    int bpr = (int)((row + 256 * 16 - 1) / (256 * 16));
-    if (bpr > 512) bpr = 512;
-    CN_DISPATCH_DT(dt, hipLaunchKernelGGL((row_scale_kernel<T>), dim3(bpr, n), dim3(256), 0, (hipStream_t)stream, (const T*)x, s, (T*)out, row, k, vec, (const T*)x2));
+    StreamPlan sp;
+    if (int e = stream_entry_plan(stream_req(SP_ROW_SCALE_DIFF, dt, n, row), dt, StreamPtrs{{x, x2, out}}, &sp)) return e;
+    const int vec = sp.path == SP_VEC;
+    CN_DISPATCH_DT(dt, hipLaunchKernelGGL((row_scale_kernel<T>), dim3(sp.gx, sp.gy), dim3(256), 0, (hipStream_t)stream, (const T*)x, s, (T*)out, row, k, vec, (const T*)x2));
     CN_LAUNCH_CHECK();
     return CN_OK;
 }
 extern "C" int cn_tap_bwd(const void* y, const void* target, const void* g, const float* s, void* out, int n, size_t row, float k,
                           int act, float slope, int dt, void* stream) {
     CN_CHECK_ARG(y && target && s && out && n > 0 && row > 0 && (dt == CN_F32 || dt == CN_BF16), "tap_bwd: bad args");
-    const int vec = alv(y, dt) && alv(target, dt) && alv(out, dt) && (!g || alv(g, dt)) && row % 4 == 0;
-    int bpr = (int)((row + 256 * 16 - 1) / (256 * 16));
-    if (bpr > 512) bpr = 512;
-    CN_DISPATCH_DT(dt, hipLaunchKernelGGL((tap_bwd_kernel<T>), dim3(bpr, n), dim3(256), 0, (hipStream_t)stream, (const T*)y, (const T*)target,
+    StreamPlan sp;
+    if (int e = stream_entry_plan(stream_req(SP_TAP_BWD, dt, n, row), dt, StreamPtrs{{y, target, g, out}}, &sp)) return e;
+    const int vec = sp.path == SP_VEC;
+    CN_DISPATCH_DT(dt, hipLaunchKernelGGL((tap_bwd_kernel<T>), dim3(sp.gx, sp.gy), dim3(256), 0, (hipStream_t)stream, (const T*)y, (const T*)target,
                                           (const T*)g, s, (T*)out, row, k, vec, act, slope));
     CN_LAUNCH_CHECK();
     return CN_OK;
@@ -1377,47 +1501,49 @@ extern "C" int cn_masked_diff(const float* a, const float* b, const uint8_t* mas
 }
 extern "C" int cn_maxpool_fwd(const void* x, void* y, int n, int h, int w, int c, int k, int s, int pad, int dt, void* stream) {
     CN_CHECK_ARG(x && y && n > 0 && h > 0 && w > 0 && c > 0 && k > 0 && s > 0 && pad >= 0 && (dt == CN_F32 || dt == CN_BF16), "maxpool: bad args");
-    const int oh = (h + 2 * pad - k) / s + 1, ow = (w + 2 * pad - k) / s + 1;
-    const size_t total = (size_t)n * oh * ow * c;
-    if (c % 4 == 0 && alv(x, dt) && alv(y, dt) && total / 4 < (1UL << 30) && (size_t)n * h * w * c / 4 < (1UL << 30)) {
-        CN_DISPATCH_DT(dt, hipLaunchKernelGGL((maxpool_fwd4_kernel<T>), dim3(ew_blocks(total / 4)), dim3(256), 0, (hipStream_t)stream,
+    StreamPlan sp;
+    if (int e = stream_entry_plan(pool_req(SP_MAXPOOL_FWD, dt, n, h, w, c, k, s, pad), dt, StreamPtrs{{x, y}}, &sp)) return e;
+    const int oh = sp.oh, ow = sp.ow;
+    if (sp.path == SP_VEC) {
+        CN_DISPATCH_DT(dt, hipLaunchKernelGGL((maxpool_fwd4_kernel<T>), dim3(sp.gx), dim3(256), 0, (hipStream_t)stream,
                                               (const T*)x, (T*)y, n, h, w, c / 4, oh, ow, k, s, pad));
         CN_LAUNCH_CHECK();
         return CN_OK;
     }
-    CN_DISPATCH_DT(dt, hipLaunchKernelGGL((maxpool_fwd_kernel<T>), dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, n, h, w, c, oh, ow, k, s, pad));
+    CN_DISPATCH_DT(dt, hipLaunchKernelGGL((maxpool_fwd_kernel<T>), dim3(sp.gx), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, n, h, w, c, oh, ow, k, s, pad));
     CN_LAUNCH_CHECK();
     return CN_OK;
 }
 extern "C" int cn_avgpool3_same(const void* x, void* y, int n, int h, int w, int c, int dt, void* stream) {
     CN_CHECK_ARG(x && y && n > 0 && h > 0 && w > 0 && c > 0 && (dt == CN_F32 || dt == CN_BF16), "avgpool3_same: bad args");
-    const bool v4 = c % 4 == 0 && alv(x, dt) && alv(y, dt);
-    const size_t total = (size_t)n * h * w * (v4 ? c / 4 : c);
+    StreamPlan sp;
+    if (int e = stream_entry_plan(pool_req(SP_AVGPOOL3_SAME, dt, n, h, w, c, 3, 1, 1), dt, StreamPtrs{{x, y}}, &sp)) return e;
     CN_DISPATCH_DT(dt, {
-        if (v4) hipLaunchKernelGGL((avgpool3_same_kernel<4, T>), dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, n, h, w, c);
-        else hipLaunchKernelGGL((avgpool3_same_kernel<1, T>), dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, n, h, w, c);
+        if (sp.path == SP_VEC) hipLaunchKernelGGL((avgpool3_same_kernel<4, T>), dim3(sp.gx), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, n, h, w, c);
+        else hipLaunchKernelGGL((avgpool3_same_kernel<1, T>), dim3(sp.gx), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, n, h, w, c);
     });
     CN_LAUNCH_CHECK();
     return CN_OK;
 }
 extern "C" int cn_maxpool_bwd(const void* x, const void* gy, void* gx, int n, int h, int w, int c, int k, int s, int pad, int dt, void* stream) {
     CN_CHECK_ARG(x && gy && gx && n > 0 && h > 0 && w > 0 && c > 0 && k > 0 && s > 0 && pad >= 0 && (dt == CN_F32 || dt == CN_BF16), "maxpool_bwd: bad args");
-    const int oh = (h + 2 * pad - k) / s + 1, ow = (w + 2 * pad - k) / s + 1;
-    const size_t total = (size_t)n * h * w * c;
-    if (k == 2 && s == 2 && pad == 0 && h % 2 == 0 && w % 2 == 0 && c % 4 == 0 && alv(x, dt) && alv(gy, dt) && alv(gx, dt)) {
+    StreamPlan sp;
+    if (int e = stream_entry_plan(pool_req(SP_MAXPOOL_BWD, dt, n, h, w, c, k, s, pad), dt, StreamPtrs{{x, gy, gx}}, &sp)) return e;
+    const int oh = sp.oh, ow = sp.ow;
+    if (sp.path == SP_POOL2) {
         const long windows4 = (long)n * oh * ow * (c / 4);
-        CN_DISPATCH_DT(dt, hipLaunchKernelGGL((maxpool2_bwd_kernel<T>), dim3(ew_blocks((size_t)windows4)), dim3(256), 0, (hipStream_t)stream,
+        CN_DISPATCH_DT(dt, hipLaunchKernelGGL((maxpool2_bwd_kernel<T>), dim3(sp.gx), dim3(256), 0, (hipStream_t)stream,
                                               (const T*)x, (const T*)gy, (T*)gx, windows4, oh, ow, c / 4));
         CN_LAUNCH_CHECK();
         return CN_OK;
     }
-    if (c % 4 == 0 && alv(x, dt) && alv(gy, dt) && alv(gx, dt) && total / 4 < 2147483647UL) {
-        CN_DISPATCH_DT(dt, hipLaunchKernelGGL((maxpool_bwd4_kernel<T>), dim3(ew_blocks(total / 4)), dim3(256), 0, (hipStream_t)stream,
+    if (sp.path == SP_VEC) {
+        CN_DISPATCH_DT(dt, hipLaunchKernelGGL((maxpool_bwd4_kernel<T>), dim3(sp.gx), dim3(256), 0, (hipStream_t)stream,
                                               (const T*)x, (const T*)gy, (T*)gx, n, h, w, c / 4, oh, ow, k, s, pad));
         CN_LAUNCH_CHECK();
         return CN_OK;
     }
-    CN_DISPATCH_DT(dt, hipLaunchKernelGGL((maxpool_bwd_kernel<T>), dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (const T*)gy, (T*)gx, n, h, w, c, oh, ow, k, s, pad));
+    CN_DISPATCH_DT(dt, hipLaunchKernelGGL((maxpool_bwd_kernel<T>), dim3(sp.gx), dim3(256), 0, (hipStream_t)stream, (const T*)x, (const T*)gy, (T*)gx, n, h, w, c, oh, ow, k, s, pad));
     CN_LAUNCH_CHECK();
     return CN_OK;
 }
@@ -1428,12 +1554,39 @@ extern "C" int cn_maxpool2_bwd_act(const void* x, const void* gy, const void* ta
                                    int w, int c, int s_rows, int dt, void* stream) {
     CN_CHECK_ARG(x && gy && gx && n > 0 && h > 0 && w > 0 && c > 0 && (dt == CN_F32 || dt == CN_BF16) && (!target || (s && (s_rows == 1 || s_rows == n))),
                  "maxpool2_bwd_act: bad args");
-    if (h % 2 || w % 2 || c % 4 || !alv(x, dt) || !alv(gy, dt) || !alv(gx, dt) || (target && !alv(target, dt))) return CN_EUNSUPPORTED;
-    const int oh = h / 2, ow = w / 2;
+    StreamPlan sp;
+    if (int e = stream_entry_plan(pool_req(SP_MAXPOOL2_BWD_ACT, dt, n, h, w, c, 2, 2, 0), dt, StreamPtrs{{x, gy, target, gx}}, &sp)) return e;
+    const int oh = sp.oh, ow = sp.ow;
     const long windows4 = (long)n * oh * ow * (c / 4);
-    CN_DISPATCH_DT(dt, hipLaunchKernelGGL((maxpool2_bwd_kernel<T>), dim3(ew_blocks((size_t)windows4)), dim3(256), 0, (hipStream_t)stream,
+    CN_DISPATCH_DT(dt, hipLaunchKernelGGL((maxpool2_bwd_kernel<T>), dim3(sp.gx), dim3(256), 0, (hipStream_t)stream,
                                           (const T*)x, (const T*)gy, (T*)gx, windows4, oh, ow, c / 4, 1, (const T*)target, s, s_rows, k));
     CN_LAUNCH_CHECK();
+    return CN_OK;
+}
+// Diagnostic: what plan_stream answers a request, without a device (include/confignet_hip.h)
+extern "C" int cn_stream_plan(int op, int dt, long long rows, size_t row, int c, int h, int w, int k, int s, int pad, unsigned aligned, int det,
+                              long long out[4]) {
+    CN_CHECK_ARG(out && op >= 0 && op < SP_OPS && (dt == CN_F32 || dt == CN_BF16) && rows > 0 && rows <= 2147483647LL, "stream_plan: bad args");
+    const bool pool = op >= SP_MAXPOOL_FWD;
+    CN_CHECK_ARG(pool || row > 0, "stream_plan: no elements");
+    CN_CHECK_ARG(!pool || (c > 0 && h > 0 && w > 0 && k > 0 && s > 0 && pad >= 0), "stream_plan: bad pool geometry");
+    CN_CHECK_ARG(op != SP_ROW_SUMSQ || dt == CN_F32, "stream_plan: row_sumsq is fp32");
+    StreamPlan sp;
+    const StreamReq r{op, dt, (long)rows, row, c, h, w, k, s, pad, aligned, det ? 1 : 0};
+    if (int e = plan_stream(r, &sp)) return e;
+    out[0] = sp.path; out[1] = sp.gx; out[2] = sp.gy; out[3] = sp.parts;
+    return CN_OK;
+}
+// The same with the mask taken from pointers by the code the entries take it with (the pointers are not dereferenced; dst_dt: the
+// type of operand 1 of a cast, ignored otherwise)
+extern "C" int cn_stream_plan_ptrs(int op, int dt, int dst_dt, long long rows, size_t row, int c, int h, int w, int k, int s, int pad,
+                                   const void* const ptrs[4], int det, long long out[4]) {
+    CN_CHECK_ARG(ptrs && op >= 0 && op < SP_OPS && (dst_dt == CN_F32 || dst_dt == CN_BF16) && (dt == CN_F32 || dt == CN_BF16), "stream_plan_ptrs: bad args");
+    return cn_stream_plan(op, dt, rows, row, c, h, w, k, s, pad, stream_mask(op, dt, dst_dt, StreamPtrs{{ptrs[0], ptrs[1], ptrs[2], ptrs[3]}}), det, out);
+}
+extern "C" int cn_stream_last_plan(long long out[5]) {
+    CN_CHECK_ARG(out, "stream_last_plan: NULL");
+    for (int i = 0; i < 5; ++i) out[i] = g_stream_last[i];
     return CN_OK;
 }
 extern "C" int cn_chan_affine3_fwd(const float* x, float* y, size_t pixels, const int* perm, float scale, const float* off, void* stream) {

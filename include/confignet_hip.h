@@ -464,6 +464,23 @@ int cn_tap_bwd(const void* y, const void* target, const void* g, const float* s,
  * s_rows = 1 (one scale) or n.  CN_EUNSUPPORTED (nothing launched) unless h, w even, c % 4 == 0, tensors 16-byte aligned. */
 int cn_maxpool2_bwd_act(const void* x, const void* gy, const void* target, const float* s, float k, void* gx, int n, int h,
                         int w, int c, int s_rows, int dt, void* stream);
+/* Diagnostic: the launch one of the fourteen streaming entries gives a request, decided by the function the entries decide with,
+ * without a device.  op: 0 act_fwd, 1 act_bwd, 2 axpby, 3 mul, 4 cast (dt = the source type), 5 sqdiff_sum, 6 row_sumsq,
+ * 7 row_scale, 8 row_scale_diff, 9 tap_bwd, 10 maxpool_fwd, 11 avgpool3_same, 12 maxpool_bwd, 13 maxpool2_bwd_act.  Flat maps and
+ * sqdiff_sum: row = numel, rows = 1; row maps: rows x row; pools: rows = n with c, h, w, k, s, pad.  aligned: bit i = the i-th tensor
+ * operand of the entry, in its argument order (scales and the reductions' `out` are not counted), may be accessed 4-wide (16 bytes
+ * in fp32, 8 in bf16); a NULL optional operand counts as aligned.  det: the deterministic mode as an argument.
+ * out = {path (0 one element per lane, 1 four per lane / 4-channel groups, 2 the 2 x 2 window kernel), grid x, grid y, floats of
+ * deterministic partials}; CN_EUNSUPPORTED where the entry refuses. */
+int cn_stream_plan(int op, int dt, long long rows, size_t row, int c, int h, int w, int k, int s, int pad, unsigned aligned, int det,
+                   long long out[4]);
+/* The same, with `aligned` taken from pointers by the function the entries take it with: ptrs[i] = operand i (NULL: absent; never
+ * dereferenced; entries beyond the operation's operands are ignored), dst_dt = the storage type of operand 1 of a cast. */
+int cn_stream_plan_ptrs(int op, int dt, int dst_dt, long long rows, size_t row, int c, int h, int w, int k, int s, int pad,
+                        const void* const ptrs[4], int det, long long out[4]);
+/* What the last of the fourteen entries called on this thread decided: out = {op, path, grid x, grid y, floats of deterministic
+ * partials}; op = -1 before any call and after a refusal.  Calls that return before planning (bad arguments, numel = 0) leave it. */
+int cn_stream_last_plan(long long out[5]);
 /* out = (a - b) * mask[n,h,w] broadcast over c (b optional) (losses.py:14) */
 int cn_masked_diff(const float* a, const float* b, const uint8_t* mask, float* out, size_t pixels, int c, void* stream);
 /* 2-D max pooling, zero padding (keras MaxPooling2D after ZeroPadding2D); bwd: the gradient of a window goes to its

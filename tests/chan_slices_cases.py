@@ -158,6 +158,55 @@ class Guarded:
             raise AssertionError("%s: %d of %d elements wrong, first at %s: got %r, want %r" % (what, len(bad), got.numel(), i, float(got[i]), float(want[i])))
 
 
+class GuardedBuf:
+    """`numel` elements of `dtype` inside a larger allocation of sentinel floats (Guarded for fp32, bf16 and uint8 views,
+    and for inputs), starting `off` elements past a vector boundary; holds `data` (an input, or an accumulator's preset) or `fill`"""
+
+    def __init__(self, numel, dtype=None, off=0, data=None, fill=NAN):
+        import torch
+        dtype = dtype or torch.float32
+        item = torch.empty((), dtype=dtype).element_size()
+        self.numel, self.dtype, self.off = int(numel), dtype, off
+        self.floats = ((self.numel + off + 8) * item + 3) // 4
+        self.buf = torch.full((self.floats + 2 * GUARD,), GUARD_VALUE, device="cuda", dtype=torch.float32)
+        self.t = self._payload(self.buf)
+        if data is not None:
+            self.t.copy_(torch.from_numpy(np.ascontiguousarray(data).reshape(-1)).to(dtype))
+        else:
+            self.t.fill_(fill)
+        self.before = self.buf.clone()
+        assert (self.t.data_ptr() - off * item) % 16 == 0
+
+    def _payload(self, buf):
+        return buf[GUARD:GUARD + self.floats].view(self.dtype)[self.off:self.off + self.numel]
+
+    @property
+    def ptr(self):
+        return self.t.data_ptr()
+
+    def unchanged(self):
+        """bit for bit what it held before the call, sentinels included"""
+        import torch
+        return torch.equal(self.buf.view(torch.int32), self.before.view(torch.int32))
+
+    def intact(self):
+        """everything around the tensor is what it was"""
+        import torch
+        cur = self.buf.clone()
+        self._payload(cur).copy_(self._payload(self.before))
+        return torch.equal(cur.view(torch.int32), self.before.view(torch.int32))
+
+    def values(self):
+        return self.t.double().cpu().numpy()
+
+    def check(self, want, what):
+        assert self.intact(), what + ": written outside the tensor"
+        got, want = self.values(), np.asarray(want, np.float64).reshape(-1)
+        if not np.array_equal(got, want):
+            bad = np.flatnonzero(~(got == want))
+            raise AssertionError("%s: %d of %d elements wrong, first at %d: got %r, want %r" % (what, len(bad), len(got), bad[0], got[bad[0]], want[bad[0]]))
+
+
 if __name__ == "__main__":
     dw_layers, bn_layers = [], []
     for batch in (32, 1):
