@@ -82,7 +82,13 @@ __device__ __forceinline__ void f2_static_for(F&& f) {
 // bf16 elements, a stage row is still 64 bytes (32 elements: one 16-byte piece = the 8 consecutive k of one MFMA operand), B is
 // always K-contiguous rows ([tap][N][K]: the two prepared filter copies of igemm_bf16.hip; flip = the data gradient walks the
 // taps backwards), the output tile goes back through LDS and leaves as 16-byte row pieces.  No K split.
-template <int WM, int WN, int TM, int TN, bool BT, bool GATHER, int KB, int NS, int NP, bool BF>
+// CB: the MFMA block.  32 = v_mfma_f32_32x32x2_f32 as described above.  16 = v_mfma_f32_16x16x4_f32 (fp32, BT, 16-deep stages, no
+// loader waves): a wave owns CB * TM rows x CB * TN columns in 16 x 16 accumulators of 4 registers, so a 64 x 48 tile (WM = 4, TN = 3)
+// pads no column of a 48-channel output where the 64 x 64 tile spends a quarter of its MFMAs and filter-row fetches on columns
+// 48 .. 63.  Lane l reads row l & 15, logical piece l >> 4 of a stage row (16 consecutive rows of one piece: the conflict-free
+// pattern again); component c of that ds_read_b128 feeds the c-th MFMA of the stage (k = 4 (l >> 4) + c: A and B permute K alike),
+// so ONE operand set covers the whole 16-deep stage and a step is 4 reads and 4 TM TN MFMAs of 32 cycles.
+template <int WM, int WN, int TM, int TN, bool BT, bool GATHER, int KB, int NS, int NP, bool BF, int CB = 32>
 __device__ __forceinline__ void fwd2_body(const CnConvGeom& g, const float* __restrict__ A, const float* __restrict__ B,
                                           const float* __restrict__ bias, float* __restrict__ C, int M, int N, int K,
                                           int act, float slope, int ntm, int ntn, long part_stride, int par,
@@ -93,11 +99,12 @@ __device__ __forceinline__ void fwd2_body(const CnConvGeom& g, const float* __re
     constexpr int KE = KB * 4 / ES;                  // elements of the reduction axis per stage
     static_assert(WM * WN == 4, "4 waves per workgroup");
     static_assert(KB == 16 || KB == 32, "stage depth");
+    static_assert(CB == 32 || (CB == 16 && BT && !BF && KB == 16 && NP == 0), "16-wide MFMA blocks: the fp32 B^T form");
     constexpr int KP = KB / 4;                       // 16-byte pieces per row and stage
     constexpr int RPI = 64 / KP;                     // rows per 1 KB wave instruction
     constexpr int FSH = KP == 4 ? 2 : 1;             // swizzle: piece ^= (row >> FSH) & (KP - 1)
-    constexpr int G = KB / 8;                        // 8-deep MFMA groups per stage
-    constexpr int BM = 32 * WM * TM, BN = 32 * WN * TN;
+    constexpr int G = CB == 16 ? 1 : KB / 8;         // MFMA groups (operand sets) per stage: 8 deep, 16-wide blocks 16 deep
+    constexpr int BM = CB * WM * TM, BN = CB * WN * TN;
     // NP = 0: the four MFMA waves also issue the LDS-DMA pieces (behind their last MFMAs).  NP = 1 / 2: that many LOADER waves
     // (waves 4 ..) issue all of them and the MFMA waves never touch the vector memory path: an LDS-DMA instruction holds its
     // wave's issue for 60 - 70 cycles -- longer than the 64-cycle shadow of the MFMA it sits behind -- and the 64 x 64 tile has
@@ -109,17 +116,20 @@ __device__ __forceinline__ void fwd2_body(const CnConvGeom& g, const float* __re
     constexpr int IB = BT ? BN / RPI : KB * BN / 256;
     constexpr int JB = (IB + NL - 1) / NL;
     constexpr int LPW = JA + JB;                     // LDS-DMA instructions per loading wave and step (dummies keep it uniform)
-    constexpr int SA = BM * KB, SB = JB * NL * 256;  // floats per stage
+    // floats per stage.  16-wide blocks: a B stage holds the IB real pieces only and the dummies of all stages land in one 1 KB
+    // block behind the stages that nobody reads -- 64 x 48 with four stages: 29 KB a workgroup, five of them on a CU (32 KB: four)
+    constexpr int SA = BM * KB, SB = CB == 16 ? IB * 256 : JB * NL * 256;
+    constexpr int SX = CB == 16 && IB < JB * NL ? 256 : 0;
     // B reads per operand set: K-contiguous rows one ds_read_b128 per tile; k-major rows one read per k row (8 bytes for two
     // adjacent columns), for a single column two k rows per ds_read2_b32 (rows 64 dwords apart: offsets 0 / 64 and 128 / 192)
     constexpr bool B2 = !BT && TN == 1 && BN == 64;
     constexpr int NB = BT ? TN : B2 ? 2 : 4 * (TN == 2 ? 1 : TN);
     constexpr int RD = TM + NB;                      // DS instructions per operand set
     static_assert((NS - 1) * LPW < 64, "vmcnt range");
-    __shared__ __attribute__((aligned(1024))) float SM[NS * (SA + SB)];     // stage s: A at s * SA, B at NS * SA + s * SB
+    __shared__ __attribute__((aligned(1024))) float SM[NS * (SA + SB) + SX];     // stage s: A at s * SA, B at NS * SA + s * SB
     __shared__ int rowmap[GATHER ? BM : 1];          // GATHER: tile row -> output row (or -1)
 
-    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, half = lane >> 5;
+    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & (CB - 1), half = lane / CB;     // (CB = 16: l15 and the quarter)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // (an SGPR: LDS-DMA destinations and tile offsets stay scalar)
     const bool loader = NP == 0 || wave >= 4, worker = wave < 4;      // (NP = 0: every wave is both)
     const int lw = NP > 0 ? wave - 4 : wave;                          // index among the loading waves
@@ -154,13 +164,15 @@ __device__ __forceinline__ void fwd2_body(const CnConvGeom& g, const float* __re
     const int ks_beg = blockIdx.z * per_z, ks_end = min(nks_all, ks_beg + per_z);
     const int nks = max(ks_end - ks_beg, 0);
 
-    f32x16 acc[TM][TN];
+    constexpr int AR = CB == 16 ? 4 : 16;            // accumulator registers per block
+    typedef float acc_t __attribute__((ext_vector_type(AR)));
+    acc_t acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+            for (int r = 0; r < AR; ++r) acc[i][j][r] = 0.f;
 
     const __amdgpu_buffer_rsrc_t ares = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), 0, (int)a_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t bres = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(B), 0, (int)b_bytes, 0x00020000);
@@ -250,6 +262,8 @@ __device__ __forceinline__ void fwd2_body(const CnConvGeom& g, const float* __re
     auto issue_piece = [&](int stage, int p) __attribute__((always_inline)) {
         if (p < JA)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(ares, (lds_float*)(SM + stage * SA + (lw + NL * p) * 256), 16, a_vo[p], a_so, 0, 0);
+        else if (CB == 16 && lw + NL * (p - JA) >= IB)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(bres, (lds_float*)(SM + NS * (SA + SB)), 16, b_vo[p - JA], b_so, 0, 0);     // (the dummy)
         else
             __builtin_amdgcn_raw_ptr_buffer_load_lds(bres, (lds_float*)(SM + NS * SA + stage * SB + (lw + NL * (p - JA)) * 256), 16,
                                                      b_vo[p - JA], b_so, 0, 0);
@@ -272,8 +286,8 @@ __device__ __forceinline__ void fwd2_body(const CnConvGeom& g, const float* __re
     // (2 gq + half) ^ f = ((half ^ f) ^ 2 gq): base with gq = 0, then XOR 32 gq on the piece field.
     const unsigned lds0 = (unsigned)(unsigned long long)(lds_float*)SM;
     const unsigned fsw = (unsigned)((l31 >> FSH) & (KP - 1));
-    const unsigned a_rd = lds0 + 4u * (unsigned)((wm * 32 * TM + l31) * KB) + 16u * ((unsigned)half ^ fsw);
-    const unsigned bt_rd = lds0 + 4u * (unsigned)(NS * SA + (wn * 32 * TN + l31) * KB) + 16u * ((unsigned)half ^ fsw);
+    const unsigned a_rd = lds0 + 4u * (unsigned)((wm * CB * TM + l31) * KB) + 16u * ((unsigned)half ^ fsw);
+    const unsigned bt_rd = lds0 + 4u * (unsigned)(NS * SA + (wn * CB * TN + l31) * KB) + 16u * ((unsigned)half ^ fsw);
     const unsigned bn_rd = lds0 + 4u * (unsigned)(NS * SA + (4 * half) * BN + wn * 32 * TN + TN * l31);
     f4 av[2][TM];
     f4 btv[2][BT ? TN : 1];
@@ -289,10 +303,10 @@ __device__ __forceinline__ void fwd2_body(const CnConvGeom& g, const float* __re
         (void)av; (void)btv; (void)bnv; (void)ap_cur; (void)bp_cur;       // (named outside the if constexpr: implicit captures)
         if (FWD2_ABLATE & 4) return;
         if constexpr (r < TM) {
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(av[set][r]) : "v"(ap_cur), "n"(4 * 32 * KB * r));
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(av[set][r]) : "v"(ap_cur), "n"(4 * CB * KB * r));
         } else if constexpr (BT) {
             constexpr int j = r - TM;
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(btv[set][BT ? j : 0]) : "v"(bp_cur), "n"(4 * 32 * KB * j));
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(btv[set][BT ? j : 0]) : "v"(bp_cur), "n"(4 * CB * KB * j));
         } else if constexpr (B2) {
             constexpr int q = 2 * (r - TM);
             f2 v;
@@ -323,6 +337,8 @@ __device__ __forceinline__ void fwd2_body(const CnConvGeom& g, const float* __re
             ua.f = av[set][i];
             ub.f = btv[set][BT ? j : 0];
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ua.h, ub.h, acc[i][j], 0, 0, 0);
+        } else if constexpr (CB == 16) {
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[set][i][q], btv[set][BT ? j : 0][q], acc[i][j], 0, 0, 0);
         } else {
             const float a = av[set][i][q];
             const float b = BT ? btv[set][BT ? j : 0][q] : bnv[set][BT ? 0 : q][j];
@@ -379,6 +395,51 @@ __device__ __forceinline__ void fwd2_body(const CnConvGeom& g, const float* __re
         // the first form of this loop (all reads of a group in one block, both LDS-DMA pieces behind one MFMA; 64 x 64 tile,
         // 144 steps, one wave per SIMD): MFMAs alone 27.7 us, LDS-DMA alone 16.3, operand reads alone 10.0, skeleton 12.6, all of
         // it 65.2 -- the SUM.  So every step is laid out as MFMA slots with at most a few instructions behind each.
+        //
+        // 16-wide blocks: one operand set per stage, so the two sets alternate between STEPS (the loop is unrolled by two for
+        // constant register names).  A step is 4 TM TN slots of 32 cycles, slot m = component m / (TM TN) on accumulator
+        // m % (TM TN) -- an accumulator comes round every TM TN slots (3 x 32 = 96 cycles for the 64 x 48 tile, above the 40-cycle
+        // dependent latency).  Slots 0 .. BAR-1 run straight off the registers; then the wait for the own pieces of step t+1 and the
+        // barrier; the four reads of step t+1 go one behind each of the next slots, and the two LDS-DMA pieces -- each holds the
+        // wave's issue for about two of these shorter slots -- behind two slots kept apart near the end.
+        if constexpr (CB == 16) {
+            constexpr int BAR = TM * TN;             // the barrier sits in front of this slot
+            constexpr int P0 = NM - 2 - NM / 4, P1 = NM - 1;      // slots of the two LDS-DMA pieces
+            static_assert(LPW == 2 && BAR + RD <= P0, "slot layout of the 16-wide step");
+            auto step = [&](auto sc, int stage, int stage_next) __attribute__((always_inline)) {
+                constexpr int set = decltype(sc)::value;
+                f2_wait_lgkm<0>();                   // the operands of this step (read behind slots BAR .. of the previous one)
+                f2_static_for<NM>([&](auto mc) __attribute__((always_inline)) {
+                    constexpr int m = decltype(mc)::value;
+                    if constexpr (m == BAR) {
+                        if (!(FWD2_ABLATE & 2)) f2_wait_vmcnt<(NS - 2) * LPW>();
+                        __builtin_amdgcn_s_barrier();
+                        __builtin_amdgcn_sched_barrier(0);
+                        read_base(stage_next, 0);
+                    }
+                    mfma_one(mc, set);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (m >= BAR && m < BAR + RD) read_op(F2Int<m - BAR>{}, set ^ 1);
+                    if constexpr (m == P0 || m == P1) {
+                        if (!(FWD2_ABLATE & 2)) {
+                            issue_piece(stage, m == P0 ? 0 : 1);
+                            if (m == P1) advance();
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                });
+            };
+            for (int t = 0; t < nks; t += 2) {
+                int st_next = st + 1 == NS ? 0 : st + 1;
+                step(F2Int<0>{}, st, st_next);
+                st = st_next;
+                if (t + 1 == nks) break;
+                st_next = st + 1 == NS ? 0 : st + 1;
+                step(F2Int<1>{}, st, st_next);
+                st = st_next;
+            }
+        }
+        if constexpr (CB == 32)
         for (int t = 0; t < nks; ++t) {
             const int st_next = st + 1 == NS ? 0 : st + 1;
             f2_wait_lgkm<0>();                       // group 0 (read during the previous step's last group)
@@ -465,6 +526,51 @@ __device__ __forceinline__ void fwd2_body(const CnConvGeom& g, const float* __re
             const int orow = GATHER ? rowmap[row] : (m0 + row < M ? m0 + row : -1), col = n0 + pc * 8;
             if (orow >= 0 && col < N)
                 *reinterpret_cast<uint4*>(Y + (long)orow * N + col) = *reinterpret_cast<const uint4*>(Cs + row * LDC + pc * 8);
+        }
+        return;
+    }
+    if constexpr (CB == 16) {
+        // epilogue of the 16-wide blocks: C/D layout col = lane & 15, row = 4 * (lane >> 4) + r.  The operation order is the 32-wide
+        // epilogue's below (no statistics: refused with bt before the launch).  Stored straight from the fragments a store
+        // instruction writes 64-byte pieces of four rows; the tile goes through the operand stages instead (free once every wave is
+        // past its last read and every LDS-DMA has landed): a wave parks its own 16 TM rows (row stride BN + 4 floats: the four row
+        // quarters of a store instruction fall on different banks) and takes them back as 16-byte pieces of whole 192-byte rows --
+        // no other wave touches them, so no second barrier.  M = 1 310 720 in isolation, two alternating pairs: 388 / 390 -> 377 / 379 us (20 x 256^2) and 368 / 371
+        // -> 348 / 353 us (80 x 128^2) against the stores straight from the fragments; M = 262 144: 79.4 / 80.1 -> 74.4 / 74.8.
+        const bool split16 = gridDim.z > 1;
+        static_assert(WN == 1, "a wave owns whole rows of the tile");
+        constexpr int LDC = BN + 4, C4 = BN / 4;
+        static_assert(BM * LDC <= NS * (SA + SB) && (16 * TM * C4) % 64 == 0, "the tile fits the operand stages");
+        __syncthreads();
+        float* const Cs = SM + wm * 16 * TM * LDC;
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int col = n0 + 16 * j + l31;
+                const float bv = (bias && blockIdx.z == 0 && col < N) ? bias[col] : 0.f;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) Cs[(16 * i + 4 * half + r) * LDC + 16 * j + l31] = acc[i][j][r] + bv;
+            }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int k = 0; k < 16 * TM * C4 / 64; ++k) {
+            const int f = lane + 64 * k, rr = f / C4, c4 = f - rr * C4;
+            const int lrow = wm * 16 * TM + rr, col = n0 + 4 * c4;
+            const int row = GATHER ? rowmap[lrow] : m0 + lrow;
+            if (row < 0 || row >= M || col >= N) continue;
+            f4 v = *reinterpret_cast<const f4*>(Cs + rr * LDC + 4 * c4);
+            float* dst = C + (long)row * N + col;
+            if (part_stride) *reinterpret_cast<f4*>(dst + (long)blockIdx.z * part_stride) = v;
+            else if (split16) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) unsafeAtomicAdd(dst + e, v[e]);
+            } else {
+                if (res) v += *reinterpret_cast<const f4*>(res + (long)row * N + col);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = cn_apply_act(v[e], act, slope);
+                *reinterpret_cast<f4*>(dst) = v;
+            }
         }
         return;
     }
@@ -558,8 +664,30 @@ __global__ __launch_bounds__(256 + 64 * NP) void fwd2_kernel(CnConvGeom g, const
                                                           b_bytes, flip, stats, stats_mode, stats_slope, srows, sper);
 }
 
+// The 64 x 48 tile on 16-wide MFMA blocks: data gradients into 48 channels (gathered rows, B = the original filter).  It takes the
+// place of the 64 x 64 tile's body in the same launch -- 64 rows a workgroup, one column tile, the same grid.
+template <int NS>
+__global__ __launch_bounds__(256) void fwd2_n48_kernel(CnConvGeom g, const float* __restrict__ A, const float* __restrict__ B,
+                                                       const float* __restrict__ bias, float* __restrict__ C, int M, int N, int K,
+                                                       int act, float slope, int ntm, int ntn, long part_stride, int par,
+                                                       const float* __restrict__ res, unsigned a_bytes, unsigned b_bytes, int flip) {
+    fwd2_body<4, 1, 1, 3, true, true, 16, NS, 0, false, 16>(g, A, B, bias, C, M, N, K, act, slope, ntm, ntn, part_stride, par, res, a_bytes,
+                                                            b_bytes, flip, nullptr, 0, 0.f, 1, 1);
+}
+
 // one workgroup per (M tile, N tile): whole rounds of the eight XCDs unless the rows are parity-ordered
 inline unsigned fwd2_grid_x(int ntm, int ntn, int par) { return (unsigned)(par ? ntm * ntn : 8 * cn_cdiv((long)ntm * ntn, 8)); }
+
+template <int NS>
+int launch2_n48(const CnConvGeom& g, const float* A, const float* B, const float* bias, float* C, long M, int N, int K, int act, float slope,
+                int splits, long part_stride, int par, hipStream_t s, const float* res, unsigned a_bytes, unsigned b_bytes) {
+    const int ntm = cn_cdiv(M, 64), ntn = cn_cdiv(N, 48);
+    dim3 grid(fwd2_grid_x(ntm, ntn, par), 1, (unsigned)splits);
+    hipLaunchKernelGGL((fwd2_n48_kernel<NS>), grid, dim3(256), 0, s, g, A, B, bias, C, (int)M, N, K, act, slope, ntm, ntn, part_stride, par, res,
+                       a_bytes, b_bytes, 1);
+    CN_LAUNCH_CHECK();
+    return CN_OK;
+}
 
 template <int WM, int WN, int TM, int TN, bool BT, bool GATHER, int KB, int NS, int NP, bool BF = false>
 int launch2(const CnConvGeom& g, const float* A, const float* B, const float* bias, float* C, long M, int N, int K, int act, float slope,
@@ -591,6 +719,12 @@ void cn_fwd2_grid(int cfg, long M, int N, int par, int splits, int grid[3]) {
     grid[0] = (int)fwd2_grid_x(cn_cdiv(M, bm), cn_cdiv(N, bn), par);
     grid[1] = 1;
     grid[2] = splits;
+}
+
+// The MFMA column block of a cn_fwd2 launch (kb / np as resolved there): 16 = the 64 x 48 body for gathered B^T launches of the
+// 64 x 64 tile with exactly 48 output channels on the default loop, else 32.  Same grid either way.
+extern "C" int cn_fwd2_col_block(int cfg, int bt, int gathered, int n, int kb, int np) {
+    return (cfg == 2 && bt && gathered && n == 48 && kb == 16 && np == 0) ? 16 : 32;
 }
 
 // The contract stated in common.h: tile cfg 0 / 1 / 2 / 4, bt = B is the original filter [N][K] (data gradient), split-K
@@ -634,6 +768,10 @@ int cn_fwd2(const CnConvGeom* gp, int cfg, int bt, const float* A, const float* 
         case 0: L2(2, 2, 2, 2);
         case 1: L2(2, 2, 2, 1);
         case 2:
+            if (cn_fwd2_col_block(cfg, bt, gp != nullptr, N, kb, np) == 16) {
+                if (ns == 3) return launch2_n48<3>(*gp, A, B, bias, C, M, N, K, act, slope, splits, part_stride, par, s, res, ab, bb);
+                return launch2_n48<4>(*gp, A, B, bias, C, M, N, K, act, slope, splits, part_stride, par, s, res, ab, bb);
+            }
             if (kb == 32) { L3(2, 2, 1, 1, 32, 3, 0); }
             if (np == 1) { if (ns == 3) { L3(2, 2, 1, 1, 16, 3, 1); } else { L3(2, 2, 1, 1, 16, 4, 1); } }
             if (np == 2) { if (ns == 3) { L3(2, 2, 1, 1, 16, 3, 2); } else { L3(2, 2, 1, 1, 16, 4, 2); } }

@@ -251,6 +251,11 @@ int cn_conv_fwd_plan(const CnConvGeom* g, int bt, int has_bias, int act, int has
  * layers it can take, -1 = the built-in choice; kb = 16 / 32 its stage depth (0 = default), ns = 3 / 4 its stage count (0 = default),
  * np = 0 / 1 / 2 its loader waves (waves that only issue the LDS-DMA; -1 = default). */
 int cn_conv_loop_select(int loop, int kb, int ns, int np);
+/* Diagnostic: the MFMA column block the LDS-DMA loop uses for a launch of tile cfg, decided exactly as the launch decides it: 16 (the
+ * 64 x 48 body on v_mfma_f32_16x16x4_f32, no padded columns) for a gathered (gathered = 1: not the plain 1x1 product) data gradient
+ * from the original filter (bt = 1) into exactly n = 48 channels on the 64 x 64 tile (cfg = 2) with the default loop (kb = 16 deep
+ * stages, np = 0 loader waves; 3 or 4 stages alike), else 32.  The grid is the same for both. */
+int cn_fwd2_col_block(int cfg, int bt, int gathered, int n, int kb, int np);
 /* Backward of the folded nearest x2 upsample: out[n,p,c] = sum of the 2^nd children of p. */
 int cn_sumpool2(const void* gu, void* gx, int nd, int n, int d, int h, int w, int c, int dt, void* stream);
 
