@@ -34,8 +34,49 @@ def input_grads_only():
         _INPUT_GRADS_ONLY = prev
 
 
+class _RefuseFn(Function):
+    """Identity on the first n_out tensors, with edges to the rest: its backward raises.  See _first_order_only."""
+
+    @staticmethod
+    def forward(ctx, name, n_out, *ts):
+        ctx.name = name
+        return tuple(t.detach() for t in ts[:n_out])
+
+    @staticmethod
+    def backward(ctx, *gs):
+        raise RuntimeError("%s is first-order only: its backward is a kernel call that cannot be differentiated again" % ctx.name)
+
+
+def _first_order_only(name, outs, *deps):
+    """Guard of a backward that is a plain kernel call: `outs` (its results, None allowed) carry no graph, so under create_graph=True
+    a derivative taken through them would come out as a silent zero.  Here they are tied to `deps` -- the cotangents and saved
+    inputs they were computed from -- by a node whose backward raises.  (torch's once_differentiable does not do that: its error
+    node has no edge to the inputs, so autograd.grad(..., allow_unused=True) and backward(inputs=...) never run it and return
+    None.)"""
+    if not torch.is_grad_enabled():
+        return outs
+    live = [i for i, o in enumerate(outs) if torch.is_tensor(o)]
+    deps = [d for d in deps if torch.is_tensor(d) and d.requires_grad]
+    if not live or not deps:
+        return outs
+    wrapped = _RefuseFn.apply(name, len(live), *[outs[i] for i in live], *deps)
+    outs = list(outs)
+    for i, w in zip(live, wrapped):
+        outs[i] = w
+    return tuple(outs)
+
+
 def _cg(t):
     return t if t.is_contiguous() else t.contiguous()
+
+
+def _bias_grad(gy, first_order, sink=None):
+    """Bias gradient of a layer without fused activation.  First order: ops.bias_grad (into the sink's slot where there is one).
+    Under create_graph: the same channel sums through NcSumDotFn, so that the result stays on the tape (d gb / d gy is a
+    broadcast, which NcLinFn provides)."""
+    if first_order:
+        return ops.bias_grad(gy.detach(), sink=sink)
+    return NcSumDotFn.apply(gy, None, True)[0].reshape(-1)
 
 
 # =============================================================================================
@@ -84,7 +125,7 @@ class ConvFn(Function):
             ops.bias_grad(gy.detach(), sink=b_slot)
         gx = gw = gb = None
         if want_b and b_slot is None:
-            gb = gb_fused if gb_fused is not None else ops.bias_grad(gy.detach())
+            gb = gb_fused if gb_fused is not None else _bias_grad(gy, first_order)
         if ops.upfold_ok(ctx.g) and first_order:
             # first-order backward of the collapsed form: data gradient straight at the stored extent (no upsampled gradient,
             # no sum-pool pass), filter gradient of the class filters scattered back to the k taps
@@ -226,7 +267,7 @@ class LinearFn(Function):
                     gw = MatmulFn.apply(x, gy, True, False)
             if ctx.has_bias and ctx.needs_input_grad[2]:
                 slot = ops.sink_for(ctx.bias_ref) if (first_order and ctx.bias_ref is not None) else None
-                gb = ops.bias_grad(gy.detach(), sink=slot)
+                gb = _bias_grad(gy, first_order, sink=slot)
         return gx, gw, gb
 
 
@@ -791,7 +832,7 @@ class MaxPoolFn(Function):
     @staticmethod
     def backward(ctx, gy):
         (x,) = ctx.saved_tensors
-        return ops.maxpool_bwd(x, _cg(gy), *ctx.cfg), None, None, None
+        return _first_order_only("MaxPoolFn", (ops.maxpool_bwd(x, _cg(gy), *ctx.cfg), None, None, None), x, gy)
 
 
 def maxpool(x, k, s, pad=0):
@@ -806,7 +847,7 @@ class ChanAffine3Fn(Function):
 
     @staticmethod
     def backward(ctx, gy):
-        return ops.chan_affine3_bwd(_cg(gy), ctx.perm, ctx.scale), None, None, None
+        return _first_order_only("ChanAffine3Fn", (ops.chan_affine3_bwd(_cg(gy), ctx.perm, ctx.scale), None, None, None), gy)
 
 
 def caffe_preprocess(x):
@@ -830,7 +871,7 @@ class Rotate3dFn(Function):
     def backward(ctx, gout):
         grid, rot = ctx.saved_tensors
         ggrid, grot = ops.rotate3d_bwd(grid, rot, _cg(gout), ctx.needs_input_grad[1])
-        return ggrid, grot
+        return _first_order_only("Rotate3dFn", (ggrid, grot), grid, rot, gout)
 
 
 class EulerMatrixFn(Function):
@@ -844,10 +885,11 @@ class EulerMatrixFn(Function):
         return ops.euler_matrix(angles)
 
     @staticmethod
-    @torch.autograd.function.once_differentiable      # (a raw kernel: a double backward through the angles must raise, not treat
-    def backward(ctx, g):                              # the Jacobian as constant -- euler_angles_to_matrix_composite is the twice
-        (angles,) = ctx.saved_tensors                  # differentiable form)
-        return ops.euler_matrix_bwd(angles, _cg(g)).reshape(ctx.shape)
+    def backward(ctx, g):
+        # a raw kernel: a double backward through the angles must raise, not treat the Jacobian as constant --
+        # euler_angles_to_matrix_composite is the twice differentiable form
+        (angles,) = ctx.saved_tensors
+        return _first_order_only("EulerMatrixFn", (ops.euler_matrix_bwd(angles, _cg(g)).reshape(ctx.shape),), angles, g)
 
 
 def euler_angles_to_matrix(angles):
@@ -883,7 +925,7 @@ class SqDiffSumFn(Function):
     @staticmethod
     def backward(ctx, g):
         a, b = ctx.saved_tensors
-        return ops.row_scale_diff(a, b, _cg(g.reshape(1)), 2.0 * ctx.scale), None, None
+        return _first_order_only("SqDiffSumFn", (ops.row_scale_diff(a, b, _cg(g.reshape(1)), 2.0 * ctx.scale), None, None), a, b, g)
 
 
 class SqDiffGroupSumFn(Function):
@@ -909,7 +951,7 @@ class SqDiffGroupSumFn(Function):
     def backward(ctx, g):
         a, b = ctx.saved_tensors
         s = torch.cat([g[i:i + 1].expand(sz) * (1.0 / (sz * ctx.per)) for i, sz in enumerate(ctx.sizes)]).contiguous()
-        return ops.row_scale_diff(a, b, s, 2.0), None, None
+        return _first_order_only("SqDiffGroupSumFn", (ops.row_scale_diff(a, b, s.detach(), 2.0), None, None), a, b, g)
 
 
 def mse_group_sums(a, b, sizes):
@@ -948,7 +990,9 @@ class RowScaleFn(Function):
         gx = RowScaleFn.apply(g, s, ctx.k) if ctx.needs_input_grad[0] else None
         gs = None
         if ctx.needs_input_grad[1]:
-            gs = ctx.k * (ops.mul(_cg(g), x).reshape(x.shape[0], -1).sum(dim=1))
+            # k * sum_row(g x) through NcSumDotFn (one channel, the row as the spatial axis): it stays on the tape under create_graph
+            n = x.shape[0]
+            gs = ctx.k * NcSumDotFn.apply(_cg(g).reshape(n, -1, 1), x.reshape(n, -1, 1), False)[1].reshape(n)
         return gx, gs, None
 
 
@@ -968,7 +1012,7 @@ class MaskedDiffFn(Function):
     def backward(ctx, g):
         (mask,) = ctx.saved_tensors
         gm = ops.masked_diff(_cg(g), None, mask)
-        return ops.axpby(gm, None, -1.0, 0.0), None, None
+        return _first_order_only("MaskedDiffFn", (ops.axpby(gm, None, -1.0, 0.0), None, None), g)
 
 
 class GanLossFn(Function):
@@ -984,7 +1028,7 @@ class GanLossFn(Function):
     @staticmethod
     def backward(ctx, g):
         (s,) = ctx.saved_tensors
-        return ops.gan_loss_bwd(s, _cg(g.reshape(1)), ctx.label).reshape(s.shape), None
+        return _first_order_only("GanLossFn", (ops.gan_loss_bwd(s, _cg(g.reshape(1)), ctx.label).reshape(s.shape), None), s, g)
 
 
 def gan_loss(scores, label):
@@ -1009,7 +1053,7 @@ class GanLossGroupFn(Function):
         scores = ctx.saved_tensors
         gouts = [None if g is None else _cg(g.reshape(1)).float() for g in gs]
         grads = ops.gan_loss_grouped(list(scores), ctx.labels, gouts, backward=True)
-        return (None,) + tuple(g.reshape(s_.shape) for g, s_ in zip(grads, scores))
+        return _first_order_only("GanLossGroupFn", (None,) + tuple(g.reshape(s_.shape) for g, s_ in zip(grads, scores)), *scores, *gs)
 
 
 def gan_losses(scores, labels):
