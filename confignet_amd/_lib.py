@@ -23,7 +23,7 @@ class CnDepthJob(ctypes.Structure):
 
 
 class CnRowsJob(ctypes.Structure):
-    """One row-skinny dense layer of cn_gemm_rows_grouped (include/confignet_hip.h)."""
+    """One row-skinny dense layer of cn_gemm_rows_grouped / cn_gemm_rows_grouped_k (include/confignet_hip.h)."""
     _fields_ = [("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("c", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("mask", ctypes.c_void_p)] + \
                [(n_, ctypes.c_int) for n_ in ("m", "n", "k", "lda", "ldb", "ldc", "tb", "act", "accumulate")] + [("slope", ctypes.c_float)]
 
@@ -86,6 +86,8 @@ SIGNATURES = {
     "cn_gemm_depth_grouped": [_p, _i, _p],
     "cn_gan_loss_grouped": [_p, _i, _i, _p],
     "cn_gemm_rows_grouped": [_p, _i, _p],
+    "cn_gemm_rows_grouped_k": [_p, _i, _p],
+    "cn_gemm_rows_grouped_plan": [_p, _i, ctypes.POINTER(_i), _i, ctypes.POINTER(_i)],
     "cn_conv_tune": [_i, _i, ctypes.c_long],
     "cn_conv_fwd_plan": [_G, _i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int * 8)],
     "cn_conv_loop_select": [_i, _i, _i, _i],

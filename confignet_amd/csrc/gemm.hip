@@ -362,6 +362,94 @@ __global__ __launch_bounds__(256) void gemm_rows_grouped_kernel(RowsJobs J) {
     }
 }
 
+// ---- the same launch for any K: the A block is staged in chunks of KC = 8192 / MT columns (the LDS block of the kernel above at
+// its limit), wave q walks quarter q of every chunk and keeps its sums in registers from chunk to chunk, so the K quarters are
+// still combined once, in the same order, after the last chunk.  A job with K <= KC takes one chunk: the multiply-adds of
+// gemm_rows_grouped_kernel in its order (measured: the same bits in rows 0..29; in rows 30 and 31 of MT = 32 hipcc fuses the
+// multiply-add of one kernel and not of the other, one rounding apart -- tests/test_gemm_rows_ksteps_gpu.py).  Launches that fit
+// the whole block never come here (plan_rows_group).  The chunk count comes from the job alone (j is wave- and workgroup-uniform), so every barrier of the
+// loop is reached by all 256 threads; the n < N guard sits inside, around the loads of B only.
+template <int MT>
+__global__ __launch_bounds__(256) void gemm_rows_grouped_ksteps_kernel(RowsJobs J) {
+    constexpr int KC = 8192 / MT;
+    extern __shared__ float sm[];                 // A chunk [MT][len <= KC] (rows >= M are zero); at MT * KC the partial sums [3][MT][64]
+    const int bid = blockIdx.x;
+    int lo = 0, hi = J.count;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (J.blk0[mid] <= bid) lo = mid;
+        else hi = mid;
+    }
+    const int j = __builtin_amdgcn_readfirstlane(lo);
+    const int M = J.m[j], N = J.n[j], K = J.k[j], lda = J.lda[j], ldb = J.ldb[j], ldc = J.ldc[j], tb = J.tb[j];
+    const float* __restrict__ A = J.a[j];
+    const float* __restrict__ B = J.b[j];
+    float* __restrict__ C = J.c[j];
+    float* As = sm;
+    float* red = sm + MT * KC;
+    const int tid = threadIdx.x, c = tid & 63, q = tid >> 6;
+    const int n = (bid - J.blk0[j]) * 64 + c;
+    float acc[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) acc[m] = 0.f;
+    for (int k0 = 0; k0 < K; k0 += KC) {
+        const int len = min(KC, K - k0);
+        if (k0 > 0) __syncthreads();              // every wave has finished with the previous chunk
+        for (int i = tid; i < MT * len; i += 256) {
+            const int m = i / len, k = i - m * len;
+            As[i] = m < M ? A[(long)m * lda + k0 + k] : 0.f;
+        }
+        __syncthreads();
+        const int kq = (len + 3) / 4, kbeg = q * kq, kend = min(len, kbeg + kq);
+        if (n < N) {
+            if (tb) {
+                const float* __restrict__ Bn = B + (long)n * ldb + k0;
+#pragma unroll 4
+                for (int k = kbeg; k < kend; ++k) {
+                    const float b = Bn[k];
+#pragma unroll
+                    for (int m = 0; m < MT; ++m) acc[m] += As[m * len + k] * b;
+                }
+            } else {
+                const float* __restrict__ Bn = B + (long)k0 * ldb + n;
+#pragma unroll 4
+                for (int k = kbeg; k < kend; ++k) {
+                    const float b = Bn[(long)k * ldb];
+#pragma unroll
+                    for (int m = 0; m < MT; ++m) acc[m] += As[m * len + k] * b;
+                }
+            }
+        }
+    }
+    if (q > 0) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m) red[((q - 1) * MT + m) * 64 + c] = acc[m];
+    }
+    __syncthreads();
+    if (q == 0 && n < N) {
+        const float bv = J.bias[j] ? J.bias[j][n] : 0.f;
+        const float* __restrict__ mask = J.mask[j];
+        const int act = J.act[j];
+        const float slope = J.slope[j];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const float v = acc[m] + red[(0 * MT + m) * 64 + c] + red[(1 * MT + m) * 64 + c] + red[(2 * MT + m) * 64 + c] + bv;
+            if (m >= M) continue;
+            float* dst = C + (long)m * ldc + n;
+            if (mask) {
+                const float y = mask[(long)m * ldc + n];          // act'(.) from the stored activation output (sign(y) = sign(x))
+                const float d = act == CN_ACT_LRELU ? (y > 0.f ? 1.f : slope) : act == CN_ACT_RELU ? (y > 0.f ? 1.f : 0.f)
+                                : act == CN_ACT_TANH ? 1.f - y * y : 1.f;
+                *dst = v * d;
+            } else if (J.accumulate[j]) {
+                unsafeAtomicAdd(dst, v);
+            } else {
+                *dst = cn_apply_act(v, act, slope);
+            }
+        }
+    }
+}
+
 __global__ void zero_rows_kernel(float* C, int M, int N, int ldc) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < (long)M * N) C[(i / N) * ldc + i % N] = 0.f;
@@ -538,6 +626,99 @@ extern "C" int cn_gemm_rows_grouped(const CnRowsJob* jobs, int njobs, void* stre
         if (mt == 8) hipLaunchKernelGGL((gemm_rows_grouped_kernel<8>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, J);
         else if (mt == 16) hipLaunchKernelGGL((gemm_rows_grouped_kernel<16>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, J);
         else hipLaunchKernelGGL((gemm_rows_grouped_kernel<32>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, J);
+        CN_LAUNCH_CHECK();
+    }
+    return CN_OK;
+}
+
+// ---- the grouped rows product for any k: decided by plan_rows_group, performed by cn_gemm_rows_grouped_k ----
+struct RowsGroupPlan {
+    int first, count;         // the run of jobs of this launch (at most CN_ROWS_GROUP)
+    int mt;                   // instantiation, from the largest m of the run
+    int kc;                   // columns of A per chunk: 8192 / mt
+    int chunks;               // chunks the largest k of the run takes
+    int grid;                 // workgroups: sum of cdiv(n, 64)
+    size_t lds;               // dynamic LDS bytes
+    int ksteps;               // 0: the whole A block fits (mt * kmax <= 8192): gemm_rows_grouped_kernel, the launch of cn_gemm_rows_grouped;
+                              // 1: gemm_rows_grouped_ksteps_kernel
+};
+
+// Pure: the launch of the run of jobs that starts at `first`; looks at m, n and k only.
+static RowsGroupPlan plan_rows_group(const CnRowsJob* jobs, int njobs, int first) {
+    RowsGroupPlan p{};
+    p.first = first;
+    p.count = njobs - first < CN_ROWS_GROUP ? njobs - first : CN_ROWS_GROUP;
+    int mmax = 0, kmax = 0;
+    for (int q = 0; q < p.count; ++q) {
+        const CnRowsJob& d = jobs[first + q];
+        p.grid += cn_cdiv(d.n, 64);
+        mmax = d.m > mmax ? d.m : mmax;
+        kmax = d.k > kmax ? d.k : kmax;
+    }
+    p.mt = gemm_rows_mt(mmax);
+    p.kc = 8192 / p.mt;
+    p.chunks = cn_cdiv(kmax, p.kc);
+    p.ksteps = (long)p.mt * kmax <= 8192 ? 0 : 1;
+    p.lds = p.ksteps ? gemm_rows_lds(p.mt, p.kc) : gemm_rows_lds(p.mt, kmax);
+    return p;
+}
+
+// the argument checks of cn_gemm_rows_grouped, job by job (the plan query does not look at the pointers)
+static int rows_jobs_check(const char* who, const CnRowsJob* jobs, int njobs, bool pointers) {
+    CN_CHECK_ARG(njobs >= 0 && (njobs == 0 || jobs), "%s: bad arguments", who);
+    for (int q = 0; q < njobs; ++q) {
+        const CnRowsJob& d = jobs[q];
+        CN_CHECK_ARG((!pointers || (d.a && d.b && d.c)) && d.m > 0 && d.m <= 32 && d.n > 0 && d.k > 0 && d.lda >= d.k && d.ldb >= (d.tb ? d.k : d.n) && d.ldc >= d.n,
+                     "%s: job %d: m=%d n=%d k=%d (m <= 32)", who, q, d.m, d.n, d.k);
+        CN_CHECK_ARG(!(d.mask && d.accumulate) && !(d.accumulate && (d.bias || d.act != CN_ACT_NONE)),
+                     "%s: job %d: accumulate excludes mask / bias / activation", who, q);
+    }
+    return CN_OK;
+}
+
+/* out = per launch {first job, jobs, MT, KC, chunks of the largest k, grid, dynamic LDS bytes, ksteps (0: gemm_rows_grouped_kernel,
+ * 1: gemm_rows_grouped_ksteps_kernel)} */
+extern "C" int cn_gemm_rows_grouped_plan(const CnRowsJob* jobs, int njobs, int* out, int cap, int* nlaunches) {
+    const int rc = rows_jobs_check("cn_gemm_rows_grouped_plan", jobs, njobs, false);
+    if (rc != CN_OK) return rc;
+    const int launches = cn_cdiv(njobs, CN_ROWS_GROUP);
+    CN_CHECK_ARG(out && nlaunches && cap >= 8 * launches, "cn_gemm_rows_grouped_plan: %d launches need %d ints (cap = %d)", launches, 8 * launches, cap);
+    for (int l = 0; l < launches; ++l) {
+        const RowsGroupPlan p = plan_rows_group(jobs, njobs, l * CN_ROWS_GROUP);
+        const int v[8] = {p.first, p.count, p.mt, p.kc, p.chunks, p.grid, (int)p.lds, p.ksteps};
+        for (int i = 0; i < 8; ++i) out[8 * l + i] = v[i];
+    }
+    *nlaunches = launches;
+    return CN_OK;
+}
+
+// cn_gemm_rows_grouped without its LDS refusal: every job is checked before the first launch, then one launch per plan.
+extern "C" int cn_gemm_rows_grouped_k(const CnRowsJob* jobs, int njobs, void* stream) {
+    const int rc = rows_jobs_check("cn_gemm_rows_grouped_k", jobs, njobs, true);
+    if (rc != CN_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    for (int first = 0; first < njobs; first += CN_ROWS_GROUP) {
+        const RowsGroupPlan p = plan_rows_group(jobs, njobs, first);
+        RowsJobs J{};
+        int blocks = 0;
+        for (int q = 0; q < p.count; ++q) {
+            const CnRowsJob& d = jobs[first + q];
+            J.a[q] = d.a; J.b[q] = d.b; J.c[q] = d.c; J.bias[q] = d.bias; J.mask[q] = d.mask;
+            J.m[q] = d.m; J.n[q] = d.n; J.k[q] = d.k; J.lda[q] = d.lda; J.ldb[q] = d.ldb; J.ldc[q] = d.ldc;
+            J.tb[q] = d.tb; J.act[q] = d.act; J.accumulate[q] = d.accumulate; J.slope[q] = d.slope;
+            J.blk0[q] = blocks;
+            blocks += cn_cdiv(d.n, 64);
+        }
+        J.blk0[p.count] = blocks;
+        J.count = p.count;
+        const dim3 grid((unsigned)p.grid);
+#define ROWS_GROUP(MT_) do { \
+            if (p.ksteps) hipLaunchKernelGGL((gemm_rows_grouped_ksteps_kernel<MT_>), grid, dim3(256), p.lds, s, J); \
+            else hipLaunchKernelGGL((gemm_rows_grouped_kernel<MT_>), grid, dim3(256), p.lds, s, J); } while (0)
+        if (p.mt == 8) ROWS_GROUP(8);
+        else if (p.mt == 16) ROWS_GROUP(16);
+        else ROWS_GROUP(32);
+#undef ROWS_GROUP
         CN_LAUNCH_CHECK();
     }
     return CN_OK;

@@ -86,7 +86,8 @@ class HologanGenerator(Net):
         sbs = [None] * (2 + self.n_2d)
         if self.mlp_bank and all(z.dtype == torch.float32 and z.dim() == 2 and z.shape[0] <= 32 for z in [inp["z_3d_0"], inp["z_3d_1"]] + zs):
             # the AdaIN MLPs of every layer (l.119-124 of the reference build them per layer; they only read the latents): one
-            # grouped launch per MLP layer for the whole pass
+            # grouped launch per MLP layer for the whole pass.  32 rows is all the grouped launch asks: it takes any layer width
+            # (cn_gemm_rows_grouped_k), a stacked batch of 24 with its 512-wide backward products included
             sets = [w[4:8], w[10:14]] + [w[20 + 6 * j + 2:20 + 6 * j + 6] for j in range(self.n_2d)]
             sbs = F.mlp_bank([inp["z_3d_0"], inp["z_3d_1"]] + zs[:self.n_2d], sets, TF_LRELU)
         x = conv_adain(x, inp["z_3d_0"], w[2:8], C3_UP, sbs[0])       # UpSampling3D folded (l.139-142)

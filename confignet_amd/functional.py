@@ -311,7 +311,8 @@ def linear(x, w, b=None, act=ACT_NONE, slope=0.0):
 
 class MlpBankFn(Function):
     """Several two-layer MLPs (Dense -> LeakyReLU(slope) -> Dense, building_blocks.py:152-173) as ONE tape node with one grouped
-    launch per layer (cn_gemm_rows_grouped): the AdaIN MLPs of a generator pass (hologan_generator.py:119-124) -- 12 launches
+    launch per layer (cn_gemm_rows_grouped_k: up to 32 rows, any layer width -- past 8192 / MT columns the launch walks K in
+    chunks): the AdaIN MLPs of a generator pass (hologan_generator.py:119-124) -- 12 launches
     forward and ~24 backward become 2 + 2; the gradients of inputs that are the SAME tensor are added by the launch (atomics,
     <= 6 terms per element; separate outputs + autograd's add in deterministic mode).  The node runs backward once the
     cotangents of all its outputs have arrived, i.e. at the end of the generator's backward pass -- which is where the latent's

@@ -1515,8 +1515,9 @@ def gan_loss_bwd(s, gout, label):
 
 
 def gemm_rows_grouped(jobs):
-    """cn_gemm_rows_grouped: every job (a, b, c, bias | None, mask | None, trans_b, act, slope, accumulate) -- c = epi(a op(b) + bias),
-    a (m <= 32, k), contiguous fp32 2-D tensors -- in ONE launch."""
+    """cn_gemm_rows_grouped_k: every job (a, b, c, bias | None, mask | None, trans_b, act, slope, accumulate) -- c = epi(a op(b) + bias),
+    a (m <= 32, k) with any k, contiguous fp32 2-D tensors -- in ONE launch per 16 jobs.  The library decides per launch whether the
+    a blocks sit in LDS whole or go through it in K chunks (cn_gemm_rows_grouped_plan reports which)."""
     arr = (CnRowsJob * len(jobs))()
     for q, (a, b, c, bias, mask, tb, act, slope, acc) in zip(arr, jobs):
         q.a, q.b, q.c = _fptr(a).value, _fptr(b).value, _fptr(c).value
@@ -1526,7 +1527,7 @@ def gemm_rows_grouped(jobs):
         q.n = b.shape[0] if tb else b.shape[1]
         q.lda, q.ldb, q.ldc = a.shape[1], b.shape[1], c.shape[1]
         q.tb, q.act, q.accumulate, q.slope = int(tb), int(act), int(acc), float(slope)
-    check(lib.cn_gemm_rows_grouped(arr, len(jobs), _stream()), "cn_gemm_rows_grouped")
+    check(lib.cn_gemm_rows_grouped_k(arr, len(jobs), _stream()), "cn_gemm_rows_grouped_k")
 
 
 def gan_loss_grouped(scores, labels, gouts=None, backward=False):

@@ -177,7 +177,19 @@ typedef struct CnRowsJob {
     int m, n, k, lda, ldb, ldc, tb, act, accumulate;
     float slope;
 } CnRowsJob;
+/* One launch per 16 jobs, the whole a_j block in LDS: CN_EINVAL (nothing of that launch enqueued) when MT x the largest k of a
+ * launch passes 8192 floats, MT = 8 / 16 / 32 from its largest m. */
 int cn_gemm_rows_grouped(const CnRowsJob* jobs, int njobs, void* stream);
+/* The same product for any k: the same per-job argument checks, made for ALL jobs before the first launch (a refused call writes
+ * nothing), and no LDS refusal.  A launch whose MT x largest k fits 8192 floats is the launch of cn_gemm_rows_grouped (same kernel,
+ * same bits); any other stages a_j in chunks of KC = 8192 / MT columns, the K quarters of every chunk summed in registers and
+ * combined once after the last chunk (a job with k <= KC in such a launch: the first kernel's multiply-adds in its order). */
+int cn_gemm_rows_grouped_k(const CnRowsJob* jobs, int njobs, void* stream);
+/* Diagnostic: the launches cn_gemm_rows_grouped_k WOULD make, decided exactly as the call decides them, without a device; the
+ * pointers of the jobs are not looked at.  out: eight ints per launch -- first job, jobs, MT, KC, chunks of the largest k,
+ * workgroups (sum of ceil(n / 64)), dynamic LDS bytes, ksteps (0: the kernel of cn_gemm_rows_grouped, 1: the chunked one);
+ * *nlaunches = ceil(njobs / 16).  CN_EINVAL for what the call would refuse and for cap < 8 * launches ints of room in out. */
+int cn_gemm_rows_grouped_plan(const CnRowsJob* jobs, int njobs, int* out, int cap, int* nlaunches);
 /* The GAN losses of every head of one discriminator call in one launch (round 6; losses.py:7-11, 20-47: six heads per call).
  * backward = 0: out[0] = mean(label softplus(-s) + (1 - label) softplus(s)) over the n scores s.  backward = 1: out[i] = the
  * gradient w.r.t. s[i] for the scalar's cotangent gout[0] (gout NULL: zero).  `jobs` is a HOST array. */
