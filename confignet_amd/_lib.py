@@ -72,7 +72,8 @@ SIGNATURES = {
     "cn_conv_dgrad": [_G, _p, _p, _p, _p],
     "cn_conv_dgrad_w": [_G, _p, _p, _p, _p],
     "cn_conv_dgrad_w_res": [_G, _p, _p, _p, _p, _p],
-    "cn_bn_fold_bwd": [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p],
+    "cn_bn_fold_bwd_chunks": [],
+    "cn_bn_fold_bwd": [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p],
     "cn_conv_wgrad_thin_partials": [],
     "cn_conv_wgrad_thin": [_G, _p, _p, _p, _p, _i, _p],
     "cn_conv_wgrad": [_G, _p, _p, _p, _i, _p],
@@ -82,6 +83,8 @@ SIGNATURES = {
     "cn_conv_wgrad_dt_workspace_bytes": [_G, _i, _i, ctypes.POINTER(_z)],
     "cn_conv_wgrad_dt": [_G, _p, _i, _p, _i, _p, _i, _p, _z, ctypes.POINTER(_i), _p],
     "cn_conv_wgrad_plan": [_G, _i, _i, _i, ctypes.c_uint, _i, ctypes.POINTER(ctypes.c_longlong)],
+    "cn_conv_wgrad_grouped": [_i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p],
+    "cn_conv_wgrad_grouped_plan": [_i, _p, _i, _p, _p],
     "cn_sum_parts_grouped": [_p, _i, _p],
     "cn_gemm_depth_grouped": [_p, _i, _p],
     "cn_gan_loss_grouped": [_p, _i, _i, _p],

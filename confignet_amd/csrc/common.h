@@ -83,9 +83,26 @@ struct Wg2Plan {
     long tiles_x, tiles_y, splits, rows;
 };
 bool cn_wgrad2_ok(const CnConvGeom& g);
-Wg2Plan cn_wgrad2_plan(const CnConvGeom& g, int forced_cfg, long wg_target);
+Wg2Plan cn_wgrad2_plan(const CnConvGeom& g, int forced_cfg, long wg_target, bool group = false);
 void cn_wgrad2(int cfg, int ns, const CnConvGeom& g, const float* x, const float* gy, float* out, long slab_stride, int rows, int tiles_x,
                int tiles_y, int splits, int accumulate, unsigned grid, hipStream_t s);
+// A grouped launch of the LDS-DMA kernel: jobs of one tile configuration, by value in the kernel arguments (< 4 KB)
+constexpr int CN_WG2_GROUP = 24, CN_KERNARG_BYTES = 4096;
+struct Wg2Job {
+    CnConvGeom g;
+    int rows, tiles_x, tiles_y, nsplits, accumulate;
+    const float* x;
+    const float* gy;
+    float* out;            // the filter gradient, or with slab_stride != 0 the slabs
+    long slab_stride;
+};
+struct Wg2Jobs {
+    Wg2Job job[CN_WG2_GROUP];
+    int blk0[CN_WG2_GROUP + 1];       // first workgroup of job j
+    int n;
+};
+static_assert(sizeof(Wg2Jobs) <= CN_KERNARG_BYTES, "the jobs of a grouped launch travel in its kernel arguments");
+void cn_wgrad2_grouped(int cfg, const Wg2Jobs& J, unsigned grid, hipStream_t s);
 void cn_igemm_wgrad(int cfg, const CnConvGeom& g, const float* x, const float* gy, float* gw, int rows, float* parts, int tx, int ty,
                     int splits, dim3 grid, hipStream_t s);
 int cn_tiny_wgrad(const CnConvGeom& g, const float* x, const float* gy, float* gw, int blocks, float* parts, hipStream_t s);

@@ -9,6 +9,7 @@
 #include "common.h"
 
 #include <algorithm>
+#include <vector>
 
 #include "mma_tile.h"
 #include "conv_geom.h"
@@ -765,6 +766,168 @@ extern "C" int cn_conv_wgrad_plan(const CnConvGeom* gp, int x_dt, int gy_dt, int
     const long long v[12] = {p.route, p.cfg, p.splits, p.rows, p.family, p.grid[0], p.grid[1], p.grid[2], (long long)p.ws_floats, p.zero, p.sum, p.stages};
     for (int i = 0; i < 12; ++i) out[i] = v[i];
     return p.ret;
+}
+
+// ---- many filter gradients in a few launches ------------------------------------------------------------------------------------
+// The filter gradients of a backward pass whose data gradients alone feed its chain (the ResNet-50 trunk: 52 of them at the exposed
+// end of the generator step) need not each fill the chip by themselves.  plan_conv_wgrad_group decides for the whole list -- tile,
+// launch, row slices, first workgroup of every job -- and is the only place that does; cn_conv_wgrad_grouped performs the plan,
+// cn_conv_wgrad_grouped_plan reports it without a device.  The slabs of the jobs with row slices always stay with the caller.
+namespace {
+
+struct WgGroupJob {
+    int cfg = -1, stages = 0, tx = 0, ty = 0, launch = 0;
+    long splits = 1, rows = 0, blk0 = 0, wgs = 0;
+    size_t ws_floats = 0;
+};
+
+bool wgrad_groupable(const CnConvGeom& g) { return cn_wgrad2_ok(g) && (long)g.k_d * g.k_h * g.k_w * g.cin >= 64; }
+
+// The rule.  A launch holds jobs of ONE tile configuration, at most CN_WG2_GROUP of them (the argument block), in the order of the
+// list; its workgroups number about two per CU -- one full round as wg2_cost models it -- and a job gets the share of them that
+// its matrix work (rows x filter elements) has in the launch's; cn_wgrad2_plan(group) turns that share into slices (whole XCD
+// rounds from 8 up, never more than the job would take alone).  Equal shares of work per workgroup are equal lifetimes: the launch
+// ends everywhere at once, most 1x1 layers need one slice or a few, and a job whose tiles alone exceed its share runs unsplit.
+// The tile is chosen first, from the job's share of the whole list (the tile that takes least of the chip), since the launches are
+// cut by it.
+// solo: every job planned as the launch of its own that cn_conv_wgrad_ws gives it (tests: the same body on the same numbers).
+// Pure: reads the geometries, cn_cu_count() and the tuning overrides.  false: a job the LDS-DMA kernel does not take.
+bool plan_conv_wgrad_group(int njobs, const CnConvGeom* g, bool solo, std::vector<WgGroupJob>& jobs, std::vector<long>& grids) {
+    jobs.assign(njobs, WgGroupJob{});
+    grids.clear();
+    std::vector<double> work(njobs);
+    double work_all = 0.0;
+    for (int j = 0; j < njobs; ++j) {
+        if (!wgrad_groupable(g[j])) return false;
+        work[j] = (double)g[j].n * g[j].out_d * g[j].out_h * g[j].out_w * g[j].k_d * g[j].k_h * g[j].k_w * g[j].cin * g[j].cout;
+        work_all += work[j];
+    }
+    const double chip = 2.0 * cn_cu_count();
+    auto share = [&](double w, double of, double launches) { return std::max(1L, (long)(chip * launches * w / of + 0.5)); };
+    const int tuned = g_tune_cfg == 0 || (g_tune_cfg >= 2 && g_tune_cfg <= 5) ? g_tune_cfg : -1;
+    // 1. the tile (solo: the whole plan)
+    for (int j = 0; j < njobs; ++j) {
+        WgGroupJob& q = jobs[j];
+        if (solo) {
+            const WgradPlan p = plan_conv_wgrad(g[j], WgradReq{CN_F32, CN_F32, true, WG_FP32_GEMM});
+            q.cfg = p.cfg; q.splits = p.splits; q.rows = p.rows; q.tx = p.tx; q.ty = p.ty;
+        } else {
+            q.cfg = cn_wgrad2_plan(g[j], tuned, share(work[j], work_all, cn_cdiv(njobs, CN_WG2_GROUP)), true).cfg;
+        }
+        q.stages = q.cfg == 3 ? 3 : 4;
+    }
+    // 2. the launches: by tile, in list order, as many jobs as the argument block holds
+    std::vector<int> open(8, -1), count;
+    std::vector<double> work_of;
+    for (int j = 0; j < njobs; ++j) {
+        int& l = open[jobs[j].cfg];
+        if (l < 0 || count[l] == CN_WG2_GROUP) {
+            l = (int)count.size();
+            count.push_back(0);
+            work_of.push_back(0.0);
+        }
+        jobs[j].launch = l;
+        ++count[l];
+        work_of[l] += work[j];
+    }
+    // 3. the slices from the job's share of its launch; the workgroup ranges, the jobs with the longest workgroups first (the
+    // hardware starts workgroups in id order as slots come free: short ones at the end fill the tail, long ones would be it)
+    grids.assign(count.size(), 0);
+    std::vector<int> order(njobs);
+    for (int j = 0; j < njobs; ++j) {
+        WgGroupJob& q = jobs[j];
+        order[j] = j;
+        if (!solo) {
+            const Wg2Plan w = cn_wgrad2_plan(g[j], q.cfg, share(work[j], work_of[q.launch], 1.0), true);
+            q.splits = w.splits; q.rows = w.rows; q.tx = (int)w.tiles_x; q.ty = (int)w.tiles_y;
+        }
+        q.wgs = (q.splits >= 8 ? cn_cdiv(q.splits, 8) * 8 : q.splits) * q.tx * q.ty;      // (the XCD-round order pads to 8 slices)
+        if (q.splits > 1) q.ws_floats = (size_t)q.splits * g[j].k_d * g[j].k_h * g[j].k_w * g[j].cin * g[j].cout;
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return jobs[a].rows > jobs[b].rows; });
+    for (int j : order) {
+        WgGroupJob& q = jobs[j];
+        q.blk0 = grids[q.launch];
+        grids[q.launch] += q.wgs;
+    }
+    for (long gr : grids)
+        if (gr >= 0x7fffffffL) return false;
+    return true;
+}
+
+}  // namespace
+
+// The grouped filter gradient (include/confignet_hip.h).  Checks everything, then launches: a refused list has enqueued nothing.
+extern "C" int cn_conv_wgrad_grouped(int njobs, const CnConvGeom* geoms, const float* const* x, const float* const* gy, float* const* out,
+                                     float* const* ws, const size_t* ws_bytes, const int* accumulate, int solo, int* parts, void* stream) {
+    CN_CHECK_ARG(njobs >= 0 && (njobs == 0 || (geoms && x && gy && out && accumulate && parts)), "cn_conv_wgrad_grouped: bad arguments");
+    for (int j = 0; j < njobs; ++j) {
+        if (int e = check_geom(geoms + j)) return e;
+        CN_CHECK_ARG(x[j] && gy[j] && out[j], "cn_conv_wgrad_grouped: job %d has a NULL tensor", j);
+    }
+    std::vector<WgGroupJob> jobs;
+    std::vector<long> grids;
+    if (!plan_conv_wgrad_group(njobs, geoms, solo != 0, jobs, grids)) {
+        cn_set_error("cn_conv_wgrad_grouped: a job the LDS-DMA filter-gradient kernel does not take");
+        return CN_EUNSUPPORTED;
+    }
+    for (int j = 0; j < njobs; ++j)
+        CN_CHECK_ARG(jobs[j].ws_floats == 0 || (ws && ws_bytes && ws[j] && ws_bytes[j] >= sizeof(float) * jobs[j].ws_floats),
+                     "cn_conv_wgrad_grouped: job %d needs a workspace of %zu bytes", j, sizeof(float) * jobs[j].ws_floats);
+    const hipStream_t s = (hipStream_t)stream;
+    std::vector<int> order(njobs);
+    for (int j = 0; j < njobs; ++j) order[j] = j;
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return jobs[a].blk0 < jobs[b].blk0; });
+    for (int l = 0; l < (int)grids.size(); ++l) {
+        Wg2Jobs J{};
+        int n = 0, cfg = -1;
+        double flops = 0.0, bytes = 0.0;
+        for (int j : order) {                   // (in the order of their first workgroups)
+            const WgGroupJob& q = jobs[j];
+            if (q.launch != l) continue;
+            const CnConvGeom& g = geoms[j];
+            const long count = (long)g.k_d * g.k_h * g.k_w * g.cin * g.cout;
+            Wg2Job& o = J.job[n];
+            o.g = g;
+            o.rows = (int)q.rows; o.tiles_x = q.tx; o.tiles_y = q.ty; o.nsplits = (int)q.splits; o.accumulate = accumulate[j] ? 1 : 0;
+            o.x = x[j]; o.gy = gy[j];
+            o.out = q.splits > 1 ? ws[j] : out[j];
+            o.slab_stride = q.splits > 1 ? count : 0;
+            J.blk0[n++] = (int)q.blk0;
+            cfg = q.cfg;
+            flops += conv_flops(g);
+            bytes += conv_bytes(g, 4.0, 4.0, 4.0);
+            parts[j] = q.splits > 1 ? (int)q.splits : 0;
+        }
+        J.blk0[n] = (int)grids[l];
+        J.n = n;
+        cn_prof_begin(s, flops, bytes, wgrad_family(cfg));
+        cn_wgrad2_grouped(cfg, J, (unsigned)grids[l], s);
+        cn_prof_end(s);
+        CN_LAUNCH_CHECK();
+    }
+    return CN_OK;
+}
+
+// Diagnostic: the plan cn_conv_wgrad_grouped WOULD follow -- needs no device, enqueues nothing.
+extern "C" int cn_conv_wgrad_grouped_plan(int njobs, const CnConvGeom* geoms, int solo, long long* out, long long info[4]) {
+    CN_CHECK_ARG(njobs >= 0 && (njobs == 0 || (geoms && out)) && info, "cn_conv_wgrad_grouped_plan: bad arguments");
+    for (int j = 0; j < njobs; ++j)
+        if (int e = check_geom(geoms + j)) return e;
+    std::vector<WgGroupJob> jobs;
+    std::vector<long> grids;
+    info[0] = 0; info[1] = CN_WG2_GROUP; info[2] = (long long)sizeof(Wg2Jobs); info[3] = CN_KERNARG_BYTES;
+    if (!plan_conv_wgrad_group(njobs, geoms, solo != 0, jobs, grids)) {
+        cn_set_error("cn_conv_wgrad_grouped: a job the LDS-DMA filter-gradient kernel does not take");
+        return CN_EUNSUPPORTED;
+    }
+    info[0] = (long long)grids.size();
+    for (int j = 0; j < njobs; ++j) {
+        const WgGroupJob& q = jobs[j];
+        const long long v[10] = {q.cfg, q.stages, q.splits, q.rows, q.tx, q.ty, q.blk0, q.wgs, q.launch, (long long)q.ws_floats};
+        for (int i = 0; i < 10; ++i) out[10 * j + i] = v[i];
+    }
+    return CN_OK;
 }
 
 // Tuning hook of the forward / data-gradient main loop (include/confignet_hip.h): loop = 1 / 0 forces the LDS-DMA loop on / off for

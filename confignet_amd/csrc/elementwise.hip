@@ -1754,15 +1754,93 @@ __global__ __launch_bounds__(256) void bn_fold_bwd_kernel(const int* __restrict_
         *gbias = o;
     }
 }
+
+// The same adjoint at streaming speed.  One workgroup per 64 columns walks all K rows of them on 16 row lanes: 288 dependent
+// read-modify-write trips for a 3x3 layer on 512 channels, and the launch lasts as long as that chain (196 us for bytes worth 55).
+// Here the rows of every segment are cut into BN_FOLD_CHUNKS chunks (grid y): d w is elementwise and complete; the chunk's
+// part of sum_k g' w goes to scratch[chunk][column] (column = its place in the concatenated coefficients), added over the row
+// lanes in lane order.  An empty chunk (K < 16) writes zeros.
+constexpr int BN_FOLD_CHUNKS = 16;
+__global__ __launch_bounds__(256) void bn_fold_bwd_rows_kernel(const int* __restrict__ seg, int nseg, const float* __restrict__ gwf,
+                                                               const float* __restrict__ arena, const float* __restrict__ a,
+                                                               float* __restrict__ gout, float* __restrict__ scratch, int ncols) {
+    const int b = blockIdx.x, chunk = blockIdx.y;
+    int lo = 0, hi = nseg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (seg[9 * mid + 8] <= b) lo = mid; else hi = mid - 1;
+    }
+    const int* sg = seg + 9 * lo;
+    const int cout = sg[3], K = sg[2] / cout;
+    const int c4 = threadIdx.x & 15, rl = threadIdx.x >> 4;
+    const int col = (b - sg[8]) * 64 + c4 * 4;
+    const int per = (K + BN_FOLD_CHUNKS - 1) / BN_FOLD_CHUNKS, r0 = chunk * per, r1 = min(K, r0 + per);
+    const float4 av = *reinterpret_cast<const float4*>(a + sg[4] + col);
+    float4 dot = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int r = r0 + rl; r < r1; r += 16) {
+        const long off = (long)r * cout + col;
+        const float4 g = *reinterpret_cast<const float4*>(gwf + sg[1] + off);
+        const float4 w = *reinterpret_cast<const float4*>(arena + sg[0] + off);
+        float4* d = reinterpret_cast<float4*>(gout + sg[0] + off);
+        float4 o = *d;
+        o.x += g.x * av.x; o.y += g.y * av.y; o.z += g.z * av.z; o.w += g.w * av.w;
+        *d = o;
+        dot.x += g.x * w.x; dot.y += g.y * w.y; dot.z += g.z * w.z; dot.w += g.w * w.w;
+    }
+    __shared__ float4 red[16][16];
+    red[rl][c4] = dot;
+    __syncthreads();
+    if (rl == 0) {
+        float4 t = red[0][c4];
+        for (int q = 1; q < 16; ++q) { const float4 u = red[q][c4]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
+        *reinterpret_cast<float4*>(scratch + (long)chunk * ncols + sg[4] + col) = t;
+    }
+}
+
+// ... and its second step: a thread per column adds the chunks' parts in chunk order (no atomics: a fixed result) and ends in the
+// coefficient algebra of bn_fold_bwd_kernel.  One workgroup of 64 threads per 64 columns, as seg[8] numbers them.
+__global__ __launch_bounds__(64) void bn_fold_bwd_cols_kernel(const int* __restrict__ seg, int nseg, const float* __restrict__ gshift,
+                                                              const float* __restrict__ a, const float* __restrict__ rs,
+                                                              const float* __restrict__ bm, float* __restrict__ gout,
+                                                              const float* __restrict__ scratch, int ncols) {
+    const int b = blockIdx.x;
+    int lo = 0, hi = nseg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (seg[9 * mid + 8] <= b) lo = mid; else hi = mid - 1;
+    }
+    const int* sg = seg + 9 * lo;
+    const int col = (b - sg[8]) * 64 + threadIdx.x, c = sg[4] + col;
+    float t = scratch[c];
+    for (int q = 1; q < BN_FOLD_CHUNKS; ++q) t += scratch[(long)q * ncols + c];
+    const float gs = gshift[c];
+    gout[sg[6] + col] += rs[c] * (t + gs * bm[c]);
+    gout[sg[7] + col] += gs;
+    gout[sg[5] + col] += a[c] * gs;
+}
 }  // namespace
 
-// The backward of cn_scale_columns_segments together with the BatchNorm coefficient algebra (real_encoder.py:13; see the kernel).
-// seg: nseg x 9 ints on the device, `blocks` = the sum over the segments of cout / 64 (every cout a multiple of 64).
+extern "C" int cn_bn_fold_bwd_chunks(void) { return BN_FOLD_CHUNKS; }
+
+// The backward of cn_scale_columns_segments together with the BatchNorm coefficient algebra (real_encoder.py:13; see the kernels).
+// seg: nseg x 9 ints on the device, `blocks` = the sum over the segments of cout / 64 (every cout a multiple of 64).  scratch:
+// cn_bn_fold_bwd_chunks() x ncols floats, ncols = the length of a / rs / bm / gshift -- the row-chunked form, two launches; NULL,
+// and always in deterministic mode (whose bits are the one-launch walk's): a workgroup per 64 columns over all rows.
 extern "C" int cn_bn_fold_bwd(const int* seg, int nseg, int blocks, const float* gwf, const float* gshift, const float* arena,
-                              const float* a, const float* rs, const float* bm, float* gout, void* stream) {
-    CN_CHECK_ARG(seg && gwf && gshift && arena && a && rs && bm && gout && nseg > 0 && blocks > 0, "bn_fold_bwd: bad args");
-    hipLaunchKernelGGL(bn_fold_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, seg, nseg, gwf, gshift, arena, a, rs,
-                       bm, gout);
+                              const float* a, const float* rs, const float* bm, float* gout, float* scratch, int ncols, void* stream) {
+    CN_CHECK_ARG(seg && gwf && gshift && arena && a && rs && bm && gout && nseg > 0 && blocks > 0 && (!scratch || ncols > 0),
+                 "bn_fold_bwd: bad args");
+    if (!scratch || cn_det()) {
+        hipLaunchKernelGGL(bn_fold_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, seg, nseg, gwf, gshift, arena, a,
+                           rs, bm, gout);
+        CN_LAUNCH_CHECK();
+        return CN_OK;
+    }
+    hipLaunchKernelGGL(bn_fold_bwd_rows_kernel, dim3((unsigned)blocks, BN_FOLD_CHUNKS), dim3(256), 0, (hipStream_t)stream, seg, nseg, gwf,
+                       arena, a, gout, scratch, ncols);
+    CN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bn_fold_bwd_cols_kernel, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, seg, nseg, gshift, a, rs, bm, gout,
+                       scratch, ncols);
     CN_LAUNCH_CHECK();
     return CN_OK;
 }

@@ -52,10 +52,10 @@ constexpr int w2_dma_before(int ja, int jb, int nslot, int ntask, int limit) {
 // front of the barrier by a constant expression.  The gather coordinates are kept in the (strided, tap-shifted) source frame and
 // advanced by mixed-radix digits with compare / select only; the three products of the offset are 24-bit multiplies (full rate;
 // cn_wgrad2_ok bounds the operands).
-template <int WM, int WN, int TM, int TN, int KB, int NS>
+template <int WM, int WN, int TM, int TN, int KB, int NS, bool GROUPED>
 __device__ __forceinline__ void wgrad2_body(const CnConvGeom& g, const float* __restrict__ X, const float* __restrict__ GY,
                                             float* __restrict__ out, long slab_stride, int rows_per_split, int tiles_x, int tiles_y,
-                                            int nsplits, int accumulate) {
+                                            int nsplits, int accumulate, int id) {
     static_assert(WM * WN == 4, "4 waves per workgroup");
     constexpr int BI = 32 * WM * TM, BN = 32 * WN * TN;
     constexpr int QA = KB * BI / 256, QB = KB * BN / 256;            // 1 KB wave instructions per stage
@@ -78,8 +78,10 @@ __device__ __forceinline__ void wgrad2_body(const CnConvGeom& g, const float* __
     __shared__ __attribute__((aligned(1024))) float SM[NS * (SA + SB)];  // stage s: A at s * SA, B at NS * SA + s * SB
 
     // XCD-aware 1-D order: workgroup id runs on XCD id % 8; every tile of ONE row slice goes to the same XCD, so the slice of X
-    // and GY that all of them read is fetched into that XCD's L2 once.  Placement only affects speed.
-    const int ntile = tiles_x * tiles_y, id = blockIdx.x;
+    // and GY that all of them read is fetched into that XCD's L2 once.  Placement only affects speed.  id: the workgroup's number
+    // within this job (blockIdx.x of a launch of its own; in a grouped launch relative to the job's first workgroup, where a
+    // constant shift of the XCDs still keeps a slice on one of them).
+    const int ntile = tiles_x * tiles_y;
     int bz, tt;
     if (nsplits >= 8) {
         const int grp = id / (8 * ntile), rr = id - grp * 8 * ntile;
@@ -327,12 +329,38 @@ __device__ __forceinline__ void wgrad2_body(const CnConvGeom& g, const float* __
 }
 
 // (the body is a device function: with generic lambdas directly inside the __global__ template hipcc 7.2 leaves the kernel's
-// host-side launch stub undefined)
+// host-side launch stub undefined; and a specialization of the body that a SECOND kernel calls fails to substitute in its host
+// pass, hence GROUPED, which nothing reads: one specialization per kernel)
 template <int WM, int WN, int TM, int TN, int KB, int NS>
 __global__ __launch_bounds__(256) void wgrad2_kernel(CnConvGeom g, const float* __restrict__ X, const float* __restrict__ GY,
                                                      float* __restrict__ out, long slab_stride, int rows_per_split, int tiles_x,
                                                      int tiles_y, int nsplits, int accumulate) {
-    wgrad2_body<WM, WN, TM, TN, KB, NS>(g, X, GY, out, slab_stride, rows_per_split, tiles_x, tiles_y, nsplits, accumulate);
+    wgrad2_body<WM, WN, TM, TN, KB, NS, false>(g, X, GY, out, slab_stride, rows_per_split, tiles_x, tiles_y, nsplits, accumulate, blockIdx.x);
+}
+
+// Many filter gradients of ONE tile configuration in one launch (the ResNet-50 trunk's backward pass leaves its filter gradients
+// to its join: none of them feeds the chain).  The jobs travel in the kernel arguments (no table copy: the step is captured in a
+// graph); a workgroup finds its job in blk0[] and runs the unchanged body with that job's numbers and its id within the job.  The
+// padded ids of a job in the XCD-round order (8 or more slices) return in the body as they do in a launch of its own; no
+// workgroup waits for another.
+template <int WM, int WN, int TM, int TN, int KB, int NS>
+__device__ __forceinline__ void wgrad2_grouped_body(const Wg2Jobs& J) {
+    const int b = blockIdx.x;
+    int lo = 0, hi = J.n;                 // job of this workgroup: blk0[lo] <= b < blk0[lo + 1]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (J.blk0[mid] <= b) lo = mid;
+        else hi = mid;
+    }
+    const int j = __builtin_amdgcn_readfirstlane(lo);
+    const Wg2Job& q = J.job[j];
+    const int id = b - J.blk0[j];
+    wgrad2_body<WM, WN, TM, TN, KB, NS, true>(q.g, q.x, q.gy, q.out, q.slab_stride, q.rows, q.tiles_x, q.tiles_y, q.nsplits, q.accumulate, id);
+}
+
+template <int WM, int WN, int TM, int TN, int KB, int NS>
+__global__ __launch_bounds__(256) void wgrad2_grouped_kernel(Wg2Jobs J) {
+    wgrad2_grouped_body<WM, WN, TM, TN, KB, NS>(J);
 }
 
 // The tiles (cfg in the implicit-GEMM numbering of cn_conv_tune; 5 = 256 x 64): rows of (tap, ci) x output channels, reduction rows
@@ -372,7 +400,12 @@ double wg2_cost(const Wg2Tile& t, long M, long Ktot, int cout, long s, long& row
 // Tile and row slices of the launch (common.h; conv_dispatch.hip: plan_conv_wgrad asks once per call).  forced: a tile of WG2_TILES
 // or -1 = the tiles the shape admits; target > 0: the slice count from that workgroup target instead of the model's best.  Some tile
 // is always considered (a forced one as it is; else 128 x 32 up to 32 output channels and 64 x 64 above), so the plan is always set.
-Wg2Plan cn_wgrad2_plan(const CnConvGeom& g, int forced, long target) {
+// group: the job shares its launch with others (conv_dispatch.hip: plan_conv_wgrad_group) and `target` is its share of the launch's
+// workgroups.  The slices are then the model's best among the counts UP TO that share (from 8 up in multiples of 8: one slice more
+// on some XCDs is a whole round there) -- a job never splits further than it would alone, where prologues and slabs already cost
+// more than the parallelism gives -- and the tile is the one that takes least of the chip: workgroups x lifetime over the share of
+// the pipes it sustains with two resident, plus its slabs; how long the job would take on an empty chip no longer matters.
+Wg2Plan cn_wgrad2_plan(const CnConvGeom& g, int forced, long target, bool group) {
     const long M = (long)g.n * g.out_d * g.out_h * g.out_w;
     const long Ktot = (long)g.k_d * g.k_h * g.k_w * g.cin;
     Wg2Plan p{};
@@ -384,19 +417,39 @@ Wg2Plan cn_wgrad2_plan(const CnConvGeom& g, int forced, long target) {
             continue;
         const long tiles = (long)cn_cdiv(Ktot, t.bi) * cn_cdiv(g.cout, t.bn);
         const long max_splits = cn_cdiv(M, 4 * t.kb);                 // a workgroup is at least 4 K steps long
-        auto consider = [&](long s_) {
-            if (s_ < 1) s_ = 1;
-            if (s_ > max_splits) s_ = max_splits;
-            long rows, splits;
-            const double us = wg2_cost(t, M, Ktot, g.cout, s_, rows, splits);
-            if (best < 0.0 || us < best) {
-                best = us;
+        auto take = [&](double score, long rows, long splits) {
+            if (best < 0.0 || score < best) {
+                best = score;
                 p.cfg = t.cfg;
                 p.tiles_x = cn_cdiv(Ktot, t.bi); p.tiles_y = cn_cdiv(g.cout, t.bn);
                 p.rows = rows; p.splits = splits;
             }
         };
-        if (target > 0) {
+        auto consider = [&](long s_) {
+            if (s_ < 1) s_ = 1;
+            if (s_ > max_splits) s_ = max_splits;
+            long rows, splits;
+            const double us = wg2_cost(t, M, Ktot, g.cout, s_, rows, splits);
+            take(us, rows, splits);
+        };
+        if (group) {
+            long cap = target <= 0 || tiles >= target ? 1 : (target + tiles / 2) / tiles;
+            if (cap >= 8) cap = (cap + 4) / 8 * 8;
+            if (cap > max_splits) cap = max_splits;
+            double us_s = -1.0;
+            long rows = 0, splits = 1;
+            auto slices = [&](long s_) {
+                long r_, n_;
+                const double us = wg2_cost(t, M, Ktot, g.cout, s_, r_, n_);
+                if (us_s < 0.0 || us < us_s) { us_s = us; rows = r_; splits = n_; }
+            };
+            for (long s_ = 1; s_ < 8 && s_ <= cap; ++s_) slices(s_);
+            for (long s_ = 8; s_ <= cap && s_ <= 1024; s_ += 8) slices(s_);
+            const double life = ((double)rows * (32.0 * (t.bi / 32) * (t.bn / 32) / 4.0) + 9000.0) / 2400.0;
+            double chip_us = (double)(tiles * splits) * life / (t.e2 * cn_cu_count());
+            if (splits > 1) chip_us += 2.0 * (double)splits * (double)Ktot * g.cout * 4.0 / 2.5e6;
+            take(chip_us, rows, splits);
+        } else if (target > 0) {
             consider(tiles >= target ? 1 : (target + tiles / 2) / tiles);
         } else {
             for (long s_ = 1; s_ < 8 && s_ <= max_splits; ++s_) consider(s_);
@@ -431,4 +484,17 @@ void cn_wgrad2(int cfg, int ns, const CnConvGeom& g, const float* x, const float
     }
 #undef WG2N
 #undef WG2
+}
+
+// One grouped launch of tile cfg (the stages a launch of its own has by default: three on the 128 x 32 tile, else four).
+void cn_wgrad2_grouped(int cfg, const Wg2Jobs& J, unsigned grid, hipStream_t s) {
+#define WG2G(WM, WN, TM, TN, KB_, NS_) hipLaunchKernelGGL((wgrad2_grouped_kernel<WM, WN, TM, TN, KB_, NS_>), dim3(grid), dim3(256), 0, s, J)
+    switch (cfg) {
+        case 0: WG2G(2, 2, 2, 2, 16, 4); break;
+        case 4: WG2G(4, 1, 1, 3, 16, 4); break;
+        case 2: WG2G(2, 2, 1, 1, 32, 4); break;
+        case 5: WG2G(4, 1, 2, 2, 16, 4); break;
+        default: WG2G(4, 1, 1, 1, 32, 3); break;
+    }
+#undef WG2G
 }

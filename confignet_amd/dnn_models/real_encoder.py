@@ -293,7 +293,9 @@ class ResNetTrunkFn(torch.autograd.Function):
     layer with bias / residual / ReLU in its epilogue -- the form the tape-free encoder has used since round 4 -- instead of a
     convolution plus a per-channel affine pass over its output.  Backward per layer: ReLU mask + shift sums in one pass
     (cn_act_bwd_bias), data gradient (a block's skip gradient added in the epilogue of its first convolution's data gradient,
-    cn_conv_dgrad_w_res, instead of by autograd's add), filter gradient WRITTEN into a packed scratch; the gradients of
+    cn_conv_dgrad_w_res, instead of by autograd's add), filter gradient WRITTEN into a packed scratch -- not between two data
+    gradients, which alone feed the chain, but recorded and issued for all layers in a few grouped launches at the end of the
+    pass (cn_conv_wgrad_grouped; the cotangents stay alive until then: 409 MB at n = 8, 818 MB at n = 16); the gradients of
     kernel / bias / gamma / beta of all 53 pairs then come out of ONE launch at the join of the pass (cn_bn_fold_bwd):
     d gamma needs sum_k g'[k][c] w[k][c] over the small filter, not a reduction of g z over the activation tensor, so the
     pre-affine convolution output z is neither kept nor read.  Same function and gradients as the composite form
@@ -364,10 +366,20 @@ class ResNetTrunkFn(torch.autograd.Function):
         def geom(ci, t):
             return enc._convs[ci][2].geom(tuple(t.shape), wf[ci].shape[-1])
 
+        later = []                                   # filter gradients left to the end of the pass: (input, cotangent, geometry, view of gwf, 0)
+
         def wgrad(ci, t_in, gu):
+            # only the data gradients feed the chain: a filter gradient the grouped launch takes is recorded (its cotangent
+            # stays alive) and issued with all the others at the join of the pass; the rest (conv1; bf16 and deterministic
+            # mode) one launch per layer here
             o, shp = views[ci]
-            if want_w:
-                ops.sink_conv_wgrad_to(t_in, gu, geom(ci, t_in), shp, gwf[o:o + int(np.prod(shp))].view(shp), defer=sunk)
+            if not want_w:
+                return
+            g_, dst = geom(ci, t_in), gwf[o:o + int(np.prod(shp))].view(shp)
+            if ops.wgrad_groupable(t_in, gu, g_):
+                later.append((t_in, gu, g_, dst, 0))
+            else:
+                ops.sink_conv_wgrad_to(t_in, gu, g_, shp, dst, defer=sunk)
 
         def relu_bwd(ci, g, y, also=None):
             """g * (y > 0) and its channel sums into the shift gradient of layer ci (and of layer `also`: a block's shortcut
@@ -413,10 +425,14 @@ class ResNetTrunkFn(torch.autograd.Function):
         gx = ops.conv_dgrad(gu0, wf[0], geom(0, x)) if ctx.needs_input_grad[1] else None
         if not want_w:
             return (None, gx) + (None,) * len(params)
+        # the recorded filter gradients, grouped, before bn_fold_bwd reads gwf: the join of the sink issues them first, then the slab
+        # sums, then the post functions; without a sink of this network's, here and now
         if sunk:
+            ops.sink_conv_wgrad_group(later)
             gout = enc.grad_arena
             ops.sink_post(lambda: ops.bn_fold_bwd(seg9, blocks, gwf, gsh, enc.arena, a, rs, bm, gout), keep=(gwf, gsh, a, rs, bm))
             return (None, gx) + (None,) * len(params)
+        ops._sum_slabs_grouped(ops.conv_wgrad_grouped(later))
         gout = torch.zeros_like(enc.arena)
         ops.bn_fold_bwd(seg9, blocks, gwf, gsh, enc.arena, a, rs, bm, gout)
         base = enc.arena.data_ptr()

@@ -612,6 +612,54 @@ def conv_wgrad(x, gy, g, w_shape, out=None, accumulate=True, defer=True, ws=None
     return gw
 
 
+WGRAD_GROUPED = True      # (False: the deferred filter gradients one launch per layer, as conv_wgrad issues them -- cross-check)
+
+
+def wgrad_groupable(x, gy, g):
+    """True where a filter gradient may be deferred to conv_wgrad_grouped: fp32 operands on a geometry the LDS-DMA kernel takes, not
+    in bf16 mode and not in deterministic mode (whose bits are those of the per-layer slice plans)."""
+    if not WGRAD_GROUPED or DETERMINISTIC or ACT_DTYPE != torch.float32 or x.dtype != torch.float32 or gy.dtype != torch.float32:
+        return False
+    out = (ctypes.c_longlong * 12)()
+    return lib.cn_conv_wgrad_plan(ctypes.byref(g), CN_F32, CN_F32, 1, 0xffffffff, -1, out) == 0 and out[0] == 3
+
+
+def conv_wgrad_grouped_plan(geoms, solo=False):
+    """(per job: tile, stages, slices, rows per slice, tiles x / y, first workgroup, workgroups, launch, workspace floats;
+    launches, jobs a launch holds, bytes of a launch's arguments, bytes an argument block holds) -- cn_conv_wgrad_grouped_plan."""
+    n = len(geoms)
+    arr = (CnConvGeom * n)(*geoms)
+    out, info = (ctypes.c_longlong * (10 * n))(), (ctypes.c_longlong * 4)()
+    check(lib.cn_conv_wgrad_grouped_plan(n, arr, int(solo), out, info), "cn_conv_wgrad_grouped_plan")
+    return [tuple(out[10 * j:10 * j + 10]) for j in range(n)], tuple(info)
+
+
+def conv_wgrad_grouped(jobs, solo=False):
+    """jobs: [(x, gy, geometry, out, accumulate)], every one wgrad_groupable.  The filter gradients of all of them in a few launches
+    that fill the chip together (cn_conv_wgrad_grouped); out is written, or added to where accumulate.  Returns the slab sums that
+    remain -- [(slabs, out, parts, count, accumulate)], the jobs of _sum_slabs_grouped -- for the jobs the plan cut into row slices;
+    the others are complete."""
+    if not jobs:
+        return []
+    n = len(jobs)
+    xs, gys = [_c(j[0]) for j in jobs], [_c(j[1]) for j in jobs]
+    plan, _ = conv_wgrad_grouped_plan([j[2] for j in jobs], solo)
+    total = sum(p[9] for p in plan)
+    ws_all = torch.empty(total, device=xs[0].device, dtype=torch.float32) if total else None
+    ws, o = [], 0
+    for p in plan:
+        ws.append(ws_all[o:o + p[9]] if p[9] else None)
+        o += p[9]
+    vp = ctypes.c_void_p * n
+    parts = (ctypes.c_int * n)()
+    check(lib.cn_conv_wgrad_grouped(n, (CnConvGeom * n)(*[j[2] for j in jobs]), vp(*[_fptr(t).value for t in xs]),
+                                    vp(*[_fptr(t).value for t in gys]), vp(*[_fptr(j[3]).value for j in jobs]),
+                                    vp(*[None if w is None else w.data_ptr() for w in ws]),
+                                    (ctypes.c_size_t * n)(*[4 * p[9] for p in plan]), (ctypes.c_int * n)(*[int(bool(j[4])) for j in jobs]),
+                                    int(solo), parts, _stream()), "cn_conv_wgrad_grouped")
+    return [(ws[k], jobs[k][3], parts[k], jobs[k][3].numel(), int(bool(jobs[k][4]))) for k in range(n) if parts[k]]
+
+
 # ---------------------------------------------------------------------------------------------
 # gradient sink: while nn.backward_into_arenas runs a backward pass, the filter / dense-weight / bias gradients are ADDED by
 # their kernels straight into the weights' slots of the networks' gradient arenas (tf.GradientTape sums the contributions of
@@ -645,6 +693,7 @@ class _Sink:
     def __init__(self, params):
         self.slots = {p.data_ptr(): p.grad for p in params if p.grad is not None}
         self.touched = []       # every stream a sink launch was issued on (a forked step has two)
+        self.wgrads = []        # (x, gy, geometry, dst, accumulate): filter gradients left to the join -> cn_conv_wgrad_grouped
         self.slabs = []         # (src, dst, parts, count, accumulate): ordered slab sums -> cn_sum_parts_grouped
         self.depth = []         # (a, b, slot): dense weight gradients a^T b -> cn_gemm_depth_grouped
         self.upfold = {}        # slot pointer -> (class-filter gradient scratch, geometry, filter shape, slot)
@@ -708,19 +757,22 @@ class grad_sink:
         others = [s_ for s_ in st.touched if s_ != cur]
         for s_ in others:                             # every stream a sink launched on (a forked step has two) before anything
             cur.wait_stream(s_)                       # below reads or adds to the arenas on the calling stream
-        slabs, depth, upfold, post, post_keep = st.slabs, st.depth, st.upfold, st.post, st.post_keep
-        st.touched, st.slabs, st.depth, st.upfold, st.post, st.post_keep = [], [], [], {}, [], []
+        wgrads, slabs, depth, upfold, post, post_keep = st.wgrads, st.slabs, st.depth, st.upfold, st.post, st.post_keep
+        st.touched, st.wgrads, st.slabs, st.depth, st.upfold, st.post, st.post_keep = [], [], [], [], {}, [], []
+        # the order of the join: 1. the filter gradients left to it, in grouped launches (their slabs join the list); 2. the slab
+        # sums and the dense weight gradients; 3. the upsample-folded scatters; 4. the post functions, which read what 1. - 3. completed
+        slabs = slabs + conv_wgrad_grouped(wgrads)
         _sum_slabs_grouped(slabs)
         _gemm_depth_grouped(depth)
-        if slabs or depth:
-            _release_operands(cur, others, [j[0] for j in slabs] + [t for j in depth for t in j[:2]])
+        if wgrads or slabs or depth:
+            _release_operands(cur, others, [t for j in wgrads for t in j[:2]] + [j[0] for j in slabs] + [t for j in depth for t in j[:2]])
         for gw2, g, w_shape, slot in upfold.values():
             upfold_wgrad(gw2, g, w_shape, out=slot, single_writer=True)
         for fn in post:                               # launches that read what the grouped reductions above have just completed
             fn()                                      # (the folded ResNet-50's parameter gradients: cn_bn_fold_bwd)
         if post:
             _release_operands(cur, others, post_keep)
-        if st.slabs or st.depth or st.upfold or st.post:                          # nothing runs after this point: work queued by a post function would be lost
+        if st.wgrads or st.slabs or st.depth or st.upfold or st.post:             # nothing runs after this point: work queued by a post function would be lost
             raise RuntimeError("a sink_post function queued work on the gradient sink after its join")
 
     def __exit__(self, exc_type, exc, tb):
@@ -752,6 +804,18 @@ def sink_conv_wgrad_to(x, gy, g, w_shape, dst, defer=True):
     conv_wgrad(x, gy, g, w_shape, out=dst, accumulate=False, defer=defer)
 
 
+def sink_conv_wgrad_group(jobs):
+    """Filter gradients that nothing in the pass waits for -- [(x, gy, geometry, dst, accumulate)], every one wgrad_groupable --
+    left to the join of the active gradient sink, which issues them grouped (and keeps their operands alive until then); issued
+    grouped here and now, slab sums included, without one."""
+    st = _SINK
+    if st is None:
+        _sum_slabs_grouped(conv_wgrad_grouped(jobs))
+        return
+    st.note_stream()
+    st.wgrads.extend(jobs)
+
+
 def sink_post(fn, keep=()):
     """Run fn() once every sink launch of the pass -- the deferred grouped reductions included -- has been issued: at the join of
     the active gradient sink, on the stream that joins; immediately without one.  fn must not queue work on the sink."""
@@ -764,10 +828,15 @@ def sink_post(fn, keep=()):
     st.post.append(fn)
 
 
-def bn_fold_bwd(seg9, blocks, gwf, gshift, arena, a, rs, bm, gout):
-    """cn_bn_fold_bwd: gout (laid out like `arena`) += the kernel / bias / gamma / beta gradients of every folded conv + BN pair."""
+def bn_fold_bwd(seg9, blocks, gwf, gshift, arena, a, rs, bm, gout, chunked=True):
+    """cn_bn_fold_bwd: gout (laid out like `arena`) += the kernel / bias / gamma / beta gradients of every folded conv + BN pair.
+    chunked: the rows of every filter cut over the grid (a scratch of chunks x columns floats, two launches); else, and in
+    deterministic mode, the one-launch walk."""
+    scratch = None
+    if chunked and not DETERMINISTIC:
+        scratch = torch.empty(lib.cn_bn_fold_bwd_chunks() * a.numel(), device=a.device, dtype=torch.float32)
     check(lib.cn_bn_fold_bwd(_ptr(seg9), seg9.shape[0], blocks, _fptr(gwf), _fptr(gshift), _fptr(arena), _fptr(a), _fptr(rs), _fptr(bm),
-                             _fptr(gout), _stream()), "cn_bn_fold_bwd")
+                             _fptr(gout), _fptr(scratch), a.numel(), _stream()), "cn_bn_fold_bwd")
 
 
 def sink_upfold_wgrad(gy, x, g2, wd_shape, g, w_shape, slot):

@@ -142,6 +142,21 @@ int cn_conv_wgrad_dt(const CnConvGeom* g, const void* x, int x_dt, const void* g
  * 1 cn_sum_parts, 2 the K = 27 kernel's own sum, 3 slabs left to the caller), stages of the LDS-DMA loop.  det: plan as in deterministic
  * mode (1) / default mode (0), -1 = the mode in force.  Returns what the call would. */
 int cn_conv_wgrad_plan(const CnConvGeom* g, int x_dt, int gy_dt, int caller_slabs, unsigned routes, int det, long long out[12]);
+/* Many filter gradients in a few launches (csrc/conv_dispatch.hip: plan_conv_wgrad_group): fp32 jobs that the LDS-DMA kernel takes
+ * (cn_conv_wgrad_plan route 3), grouped by tile into launches of up to 24 jobs whose workgroups together fill the chip -- for the
+ * filter gradients of a backward pass that nothing on its chain waits for.  All arrays are HOST arrays of njobs entries; the jobs
+ * travel in the kernel arguments.  Job j: geoms[j], x[j], gy[j]; out[j] is overwritten, or added to when accumulate[j] != 0.  A job
+ * the plan cuts into row slices writes parts[j] >= 2 partial filters into ws[j] (ws_bytes[j] >= 4 * the plan's workspace floats)
+ * and leaves out[j] untouched: the caller adds them in index order (cn_sum_parts_grouped); parts[j] = 0: out[j] is complete.
+ * solo != 0: every job with the plan cn_conv_wgrad_ws gives it alone (same numbers, same bits).  CN_EUNSUPPORTED, nothing
+ * launched: some job is not one of the kernel's. */
+int cn_conv_wgrad_grouped(int njobs, const CnConvGeom* geoms, const float* const* x, const float* const* gy, float* const* out,
+                          float* const* ws, const size_t* ws_bytes, const int* accumulate, int solo, int* parts, void* stream);
+/* Diagnostic: the plan of that call, without a device.  out: 10 numbers per job -- tile (cn_conv_tune numbering, 5 = 256x64),
+ * stages, row slices, rows per slice, tiles over filter rows / output channels, first workgroup within its launch, workgroups
+ * (padded ids of the XCD-round order included), launch, workspace in floats.  info: launches, most jobs a launch holds, bytes of
+ * a launch's argument struct, bytes an argument block holds. */
+int cn_conv_wgrad_grouped_plan(int njobs, const CnConvGeom* geoms, int solo, long long* out, long long info[4]);
 typedef struct CnSumJob {
     const float* src;     /* parts x count floats */
     float* dst;           /* count floats */
@@ -604,9 +619,14 @@ int cn_scale_columns_segments(const float* src, float* dst, const int* seg, cons
  * real_encoder.py:13 runs on the folded filters): from the folded filters' gradients gwf (packed) and the shifts' gradients
  * gshift, ADD d kernel, d bias, d gamma, d beta into gout (laid out like the weight arena `arena`).  a = gamma rs,
  * rs = rsqrt(var + eps), bm = bias - mean, concatenated per layer.  seg: nseg x 9 ints on the device -- the five of
- * cn_scale_columns_segments, the arena offsets of bias / gamma / beta, the segment's first workgroup; blocks = sum cout / 64. */
+ * cn_scale_columns_segments, the arena offsets of bias / gamma / beta, the segment's first workgroup; blocks = sum cout / 64.
+ * scratch: cn_bn_fold_bwd_chunks() * ncols floats (ncols = the length of a / rs / bm / gshift): every segment's rows are cut into
+ * that many chunks over the grid, the chunks' parts of sum_k g' w are added in chunk order by a second small launch -- no atomics, a
+ * fixed result, the launch no longer as long as the longest filter's row walk.  scratch NULL, and deterministic mode always: one
+ * launch, a workgroup per 64 columns over all rows. */
+int cn_bn_fold_bwd_chunks(void);
 int cn_bn_fold_bwd(const int* seg, int nseg, int blocks, const float* gwf, const float* gshift, const float* arena,
-                   const float* a, const float* rs, const float* bm, float* gout, void* stream);
+                   const float* a, const float* rs, const float* bm, float* gout, float* scratch, int ncols, void* stream);
 
 /* ---- HDRI environment-map encoding (hdri_encoding/hdri_pca_model.py: np.log2(x + 1), rotate_hdri = np.roll along the columns,
  * cv2.resize INTER_AREA; confignet_amd/hdri.py) -------------------------------------------------------------------------------
