@@ -104,7 +104,7 @@ ConvPlan plan_conv_fwd(const CnConvGeom& g, const ConvReq& q) {
             g.cout == 3 && g.cin == 32 && g.p_h == 1 && g.p_w == 1 && g.out_h <= 2 * g.in_h && g.out_w <= 2 * g.in_w)
             return small(CN_ROUTE_UP2K4_RGB, CN_FAM_THIN, (long)g.n * cn_cdiv(g.in_h, 8) * cn_cdiv(g.in_w, 16));
         if (img != CN_ROUTE_UNSUPPORTED) return small(img, img_family, img_grid);          // (the two data gradients into the image)
-        if (p.par && g.cin % BK == 0 && q.act == CN_ACT_NONE) return small(CN_ROUTE_THIN_PAR_IGEMM, CN_FAM_FWD_128x32, cn_cdiv(M, 128));
+        if (p.par && g.cin % BK == 0 && q.act == CN_ACT_NONE && T <= CN_MAX_MASKED_TAPS) return small(CN_ROUTE_THIN_PAR_IGEMM, CN_FAM_FWD_128x32, cn_cdiv(M, 128));
         if (p.vec && g.cout == 3 && CL >= 5 && CL <= 16 && T <= 32 && (p.par || dl1) && g.dl_d * g.dl_h * g.dl_w <= 8)
             return small(CN_ROUTE_THIN_COOP, -1, cn_cdiv(M, (256 / (CL <= 8 ? 8 : 16)) * CN_THIN_COOP_PX));
         return small(CN_ROUTE_THIN, -1, cn_cdiv(M, 256));
@@ -115,6 +115,12 @@ ConvPlan plan_conv_fwd(const CnConvGeom& g, const ConvReq& q) {
         return refuse(CN_EINVAL);
     }
     const bool vec = g.cin % BK == 0;
+    // the vectorised gathers (igemm_fwd_kernel, fwd2.hip) walk the taps of a tile through one 64-bit mask: a longer filter would lose
+    // its taps past the 64th without a word (the scalar gather, cin % 16 != 0, counts K elements and has no such limit)
+    if (vec && (long)g.k_d * g.k_h * g.k_w > CN_MAX_MASKED_TAPS) {
+        cn_set_error("%d taps: the vectorised implicit-GEMM gather takes at most %d", g.k_d * g.k_h * g.k_w, CN_MAX_MASKED_TAPS);
+        return refuse(CN_EUNSUPPORTED);
+    }
     const int par = parity_ordered(g) && vec;
     // tile choice: the biggest tile that still gives >= 2 workgroups per CU (256 CUs)
     const long t128 = (long)cn_cdiv(M, 128) * cn_cdiv(g.cout, 128);

@@ -48,6 +48,10 @@ __device__ __forceinline__ int par_row(const CnConvGeom& g, int mp, int M, int& 
     return ((n * g.out_d + xd * g.dl_d + cd) * g.out_h + xh * g.dl_h + ch) * g.out_w + xw * g.dl_w + cw;
 }
 
+// The vectorised gathers keep the live taps of a tile in one 64-bit mask (bit = tap) and walk it with ffs: they take filters of at
+// most this many taps.  The hosts refuse longer ones (plan_conv_fwd, conv_bf16); ops.upfold_ok keeps class filters below it.
+constexpr int CN_MAX_MASKED_TAPS = 64;
+
 __device__ __forceinline__ unsigned long long par_tap_mask(const CnConvGeom& g, int cls) {
     const int cw = cls % g.dl_w, ch = (cls / g.dl_w) % g.dl_h, cd = cls / (g.dl_w * g.dl_h);
     unsigned long long mask = 0ull;

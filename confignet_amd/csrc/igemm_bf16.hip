@@ -427,6 +427,7 @@ int launch_bf16(const CnConvGeom& g, int par, int flip, const bf16_t* x, const b
 int conv_bf16(const CnConvGeom& g, int flip, const bf16_t* x, const bf16_t* wb, const float* bias, bf16_t* y, int act,
               float slope, hipStream_t s) {
     if (g.cin % 8 || g.cout % 8) return CN_EUNSUPPORTED;
+    if ((long)g.k_d * g.k_h * g.k_w > CN_MAX_MASKED_TAPS) return CN_EUNSUPPORTED;      // (the tap mask of the gather: conv_geom.h)
     const long M = (long)g.n * g.out_d * g.out_h * g.out_w;
     const int par = parity_ordered(g);
     // tile choice: the biggest tile that still gives >= 2 workgroups per CU (256 CUs); these kernels are memory bound,

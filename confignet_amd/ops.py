@@ -192,9 +192,10 @@ def _weight_cache_lookup(w, slot, make):
         c = getattr(w, slot, None)
         if c is not None and c[0] == key:
             return c[1]
-        if not torch.cuda.is_current_stream_capturing():
+        if not w.is_cuda or not torch.cuda.is_current_stream_capturing():   # (a host tensor knows no stream: nothing to ask the runtime)
             val = make(w.detach())
-            torch.cuda.current_stream().synchronize()   # once per frozen filter: any stream may read the copy from now on
+            if w.is_cuda:
+                torch.cuda.current_stream().synchronize()   # once per frozen filter: any stream may read the copy from now on
             setattr(w, slot, (key, val))
             return val
         return make(w.detach())                    # first use happens inside a capture: a graph-private copy
@@ -238,12 +239,21 @@ def _bf16_conv_ok(g):
 # x2-upsample-folded convolutions collapsed per output-parity class (include/confignet_hip.h: cn_upfold_*)
 # ---------------------------------------------------------------------------------------------
 UPFOLD = True
+UPFOLD_MAX_CLASS_TAPS = 64     # the implicit-GEMM loops keep the live taps of a tile in one 64-bit mask (csrc/conv_geom.h: par_tap_mask)
+
+
+def upfold_class_taps(g):
+    """Taps of the class filters of a folded layer: per used axis k + 1 (3 for k = 2), see cn_upfold_weights."""
+    ks = (g.k_d, g.k_h, g.k_w) if g.nd == 3 else (g.k_h, g.k_w)
+    return math.prod(k + 1 if k >= 3 else 3 for k in ks)
 
 
 def upfold_ok(g):
-    """Generator layers UpSampling + Conv(k3 / k4, SAME, stride 1) with wide channels (map_final keeps its own kernel)."""
+    """Generator layers UpSampling + Conv(k2 .. k4, SAME, stride 1) with wide channels (map_final keeps its own kernel).  3-D extents
+    whose class filters pass 64 taps -- (2,4,4), (3,3,4), (3,4,4), (4,4,4) and their permutations -- stay on the unfolded path."""
     return (UPFOLD and g.up == 1 and g.cin > 4 and g.cout > 4 and g.s_d * g.s_h * g.s_w == 1 and g.dl_d * g.dl_h * g.dl_w == 1
             and all(2 <= k <= 4 for k in ((g.k_d, g.k_h, g.k_w) if g.nd == 3 else (g.k_h, g.k_w)))
+            and upfold_class_taps(g) <= UPFOLD_MAX_CLASS_TAPS
             and g.out_h == 2 * g.in_h and g.out_w == 2 * g.in_w and (g.nd == 2 or g.out_d == 2 * g.in_d))
 
 

@@ -71,7 +71,10 @@ int cn_version(void);
  *   keras.applications VGG19/VGG16/ResNet50 convs (perceptual_loss.py:19,35 ; real_encoder.py:13).
  * Which kernel runs is the library's choice by geometry alone (first-layer / thin-output / image-gradient kernels, the LDS-DMA
  * loop of fwd2.hip for every vectorisable layer, the k-major implicit-GEMM loop for the rest) -- the results are the same
- * convolution.  The library reads no environment variables; cn_conv_tune / cn_conv_loop_select force a route for sweeps and tests. */
+ * convolution.  The library reads no environment variables; cn_conv_tune / cn_conv_loop_select force a route for sweeps and tests.
+ * Filters of more than 64 taps (k_d k_h k_w; no layer of the networks) run only on the scalar gather (cin % 16 != 0): the
+ * vectorised gathers keep the live taps of a tile in a 64-bit mask, so with cin % 16 == 0 -- and in the bf16 family -- such a
+ * filter is CN_EUNSUPPORTED (nothing launched) in forward and data gradient alike. */
 int cn_conv_fwd(const CnConvGeom* g, const float* x, const float* w, const float* bias,
                 float* y, int act, float slope, void* stream);
 /* cn_conv_fwd that also returns the per-(sample, channel) sums the FOLLOWING normalisation layer needs, taken in the convolution's

@@ -95,6 +95,14 @@ def test_convolution_geometries_stay_off_winograd(name):
     assert ops.upfold_ok(g) == (name in ("f", "g"))
 
 
+@pytest.mark.parametrize("kernel,folded", [((3, 3, 3), True), ((2, 3, 4), True), ((3, 3, 4), False), ((4, 4, 4), False)])
+def test_upfold_ok_stops_where_the_class_filters_pass_64_taps(kernel, folded):
+    """f's geometry with other 3-D extents: 4 x 4 x 4 = 64 and 3 x 4 x 5 = 60 class taps are taken, 4 x 4 x 5 = 80 and 5 x 5 x 5 = 125
+    are not (the implicit-GEMM gathers hold the live taps of a tile in a 64-bit mask) and run unfolded"""
+    xs, _, cout, stride, up, epad = CE.TABLE["f"]
+    assert ops.upfold_ok(CE.geom((xs, kernel, cout, stride, up, epad))) == folded
+
+
 def test_the_comparison_notices_a_cut_graph_and_a_swapped_operand():
     """the instrument itself: a statement whose first gradient is detached before the second level, and a transposed operand"""
     case = A.TABLE["sqdiff_sum"]

@@ -487,11 +487,16 @@ UPFOLD = [("f", C.TABLE["f"]), ("g", C.TABLE["g"])] + [("upfold-%d" % i, (c[0], 
 def test_the_upsample_folded_layer_gives_the_integer_result(name, case):
     """F.conv with a folded x2 upsample runs as per-parity-class filters, which are sums of integers: forward (+ bias + LeakyReLU),
     data gradient at the stored extent and filter gradient are exact."""
+    assert len(UPFOLD) >= 4
+    upfold_layer_exact(name, case)
+
+
+def upfold_layer_exact(name, case, folded=True):
+    """the body of the test above, for tests/test_filter_prep_gpu.py as well; folded: what ops.upfold_ok must say of the layer"""
     from confignet_amd import functional as F
     from confignet_amd import ops
-    assert len(UPFOLD) >= 4
     spec = ops.ConvSpec(case[1], up=1)
-    assert ops.upfold_ok(spec.geom(case[0], case[2]))
+    assert ops.upfold_ok(spec.geom(case[0], case[2])) == folded
     inp = C.integer_inputs(case)
     x, w, b = (inp[k].float().cuda().requires_grad_(True) for k in ("x", "w", "bias"))
     xr, wr, br = (inp[k].clone().requires_grad_(True) for k in ("x", "w", "bias"))

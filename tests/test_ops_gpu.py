@@ -871,6 +871,11 @@ def test_upsample_folded_conv_collapsed_per_parity_class(case, dtype):
     gradient at the stored extent and filter gradient against the float64 oracle of UpSampling -> Conv(SAME).
     fp32: 2e-4 like every other convolution.  bf16: the oracle on the bf16-rounded x; the class filters are sums of up to 8 taps
     rounded to bf16 AFTER summing, so |err| <= 2^-8 (|y| + sum |terms|) -- asserted as 1.5e-2 of the output scale."""
+    upfold_layer_close(case, dtype)
+
+
+def upfold_layer_close(case, dtype, folded=True):
+    """the body of the test above, for tests/test_filter_prep_gpu.py as well; folded: what ops.upfold_ok must say of the layer"""
     from confignet_amd import functional as F
     from confignet_amd import ops
     xs, k, cout = case
@@ -882,7 +887,7 @@ def test_upsample_folded_conv_collapsed_per_parity_class(case, dtype):
     ops.set_activation_dtype(dtype)
     try:
         spec = ops.ConvSpec(k, up=1)
-        assert ops.upfold_ok(spec.geom(xs, cout))
+        assert ops.upfold_ok(spec.geom(xs, cout)) == folded
         xt = dev(x)
         if dtype == "bf16":
             xt = xt.to(torch.bfloat16)
