@@ -97,8 +97,25 @@ def _rng(*key):
     return np.random.default_rng(zlib.crc32(repr(key).encode()))
 
 
-def ints(key, shape, lim=3, nonzero=False, even=False, odd=False):
-    v = _rng("int", key).integers(-lim, lim + 1, size=shape).astype(np.float64)
+_SPARSE = None          # (density, lim) while the inputs of a sparse view of a case are drawn (sparse_inputs), else None
+
+
+def _thin(key, shape, density, lim):
+    """the sparse draw: magnitudes 1 .. lim, random signs, a fraction `density` of the entries kept, zero elsewhere"""
+    rng = _rng("sparse", key)
+    mag = rng.integers(1, lim + 1, size=shape).astype(np.float64)
+    sign = np.where(rng.integers(0, 2, size=shape) > 0, 1.0, -1.0)
+    return np.where(rng.random(size=shape) < density, mag * sign, 0.0)
+
+
+def ints(key, shape, lim=3, nonzero=False, even=False, odd=False, sparse=None):
+    """integers in [-lim, lim]; sparse = (density, lim): the sparse draw instead (also while sparse_inputs draws a case's inputs).
+    The conventions hold in both: even / odd are applied after the draw, nonzero turns a zero into a one."""
+    sparse = _SPARSE if sparse is None else sparse
+    if sparse is not None:
+        v = _thin(key, shape, sparse[0], min(lim, sparse[1]))
+    else:
+        v = _rng("int", key).integers(-lim, lim + 1, size=shape).astype(np.float64)
     if even:
         v = 2.0 * v
     if odd:
@@ -116,13 +133,48 @@ def reals(key, shape, scale=1.0, offset=0.0):
 def distinct(key, shape, positive=False):
     """distinct integers (no tie in any pool window), centred on zero; positive: 1 .. n (no zero of a padded border wins or ties)"""
     n = int(np.prod(shape))
+    if _SPARSE is not None:
+        # the sparse view: distinct within each channel only (a pool never compares two channels), so that no value passes the
+        # count of positions of one channel
+        c, rng = shape[-1], _rng("perm", key)
+        per = n // c
+        cols = [rng.permutation(per) - (-1 if positive else per // 2) for _ in range(c)]
+        return torch.from_numpy(np.stack(cols, axis=-1).astype(np.float64).reshape(shape))
     return torch.from_numpy((_rng("perm", key).permutation(n) - (-1 if positive else n // 2)).astype(np.float64).reshape(shape))
+
+
+def conv_ints(case, lim=3):
+    """CE.integer_inputs of a conv_edge_cases entry; while sparse_inputs draws: the sparse draw of the same tensors"""
+    i = CE.integer_inputs(case, lim=lim)
+    if _SPARSE is None:
+        return i
+    return {k: torch.from_numpy(_thin(("conv", case, k), tuple(v.shape), _SPARSE[0], min(lim, _SPARSE[1]))) for k, v in i.items()}
+
+
+def sparse_conv_ints(case, density, lim=1):
+    """conv_ints of a conv_edge_cases entry in the sparse draw"""
+    global _SPARSE
+    prev, _SPARSE = _SPARSE, (density, lim)
+    try:
+        return conv_ints(case, lim)
+    finally:
+        _SPARSE = prev
+
+
+def sparse_inputs(case, density, lim=1):
+    """case.inputs() with every integer draw replaced by the sparse one"""
+    global _SPARSE
+    prev, _SPARSE = _SPARSE, (density, lim)
+    try:
+        return case.inputs()
+    finally:
+        _SPARSE = prev
 
 
 def cotangent(case, level, index, shape, real):
     key = (case.name, "cot", level, index)
     lim = min(case.lim, 2) if case.quad else case.lim
-    return reals(key, shape) if real else ints(key, shape, lim=lim)
+    return reals(key, shape) if real else ints(key, shape, lim=lim, sparse=getattr(case, "sparse", None))
 
 
 # ---- the ladder -----------------------------------------------------------------------------------------------------------------
@@ -133,10 +185,11 @@ def _grad(outs, targets, cots, create_graph):
     return list(torch.autograd.grad([o for o, _ in live], targets, [c for _, c in live], create_graph=create_graph, allow_unused=True))
 
 
-def ladder(case, fn, t, make, order=None, absolute=False, first_pass=None, row_sumsq=None):
+def ladder(case, fn, t, make, order=None, absolute=False, first_pass=None, row_sumsq=None, make_cot=None):
     """The quantities of `case` from fn(t): {"y<j>", "d1/<input>", "d2/<input>", "d2/c<j>", "d3/..."} -> tensor | None.
     make(tensor64) turns a drawn float64 CPU tensor into the operand type (dtype, device); first_pass: a context manager factory
-    for level 1 (F.input_grads_only); row_sumsq: the product's own row_sumsq for quad cases."""
+    for level 1 (F.input_grads_only); row_sumsq: the product's own row_sumsq for quad cases; make_cot(j, tensor64): the same as
+    make for the cotangent of output j where that depends on the output (its storage type)."""
     order = case.order if order is None else order
     real = not case.exact
     for k in case.diff:
@@ -152,7 +205,8 @@ def ladder(case, fn, t, make, order=None, absolute=False, first_pass=None, row_s
         if case.used is not None and not case.used[j]:
             continue
         c = cotangent(case, 1, j, tuple(y.shape), real)
-        c = make(c.abs() if absolute else c).requires_grad_(order > 1)
+        c = c.abs() if absolute else c
+        c = (make(c) if make_cot is None else make_cot(j, c)).requires_grad_(order > 1)
         outs.append(y)
         c0.append(("c%d" % j, c))
     firsts = [t[k] for k in case.first]
@@ -198,10 +252,15 @@ def reference(case, dtype=torch.float64, order=None):
     return ladder(case, lambda t_: case.statement(t_), t, lambda v: v.to(dtype).clone(), order)
 
 
+def absolute_ladder(case, order=None):
+    """the ladder on absolute values (subtractions as additions, activations as the identity), quantity by quantity"""
+    t = inputs_as(case, torch.float64, absolute=True)
+    return ladder(case, lambda t_: case.statement(t_, absolute=True), t, lambda v: v.clone(), order, absolute=True)
+
+
 def absolute_bound(case, order=None):
     """max over every quantity of the ladder on absolute values: no partial sum of the case, at any order, is larger"""
-    t = inputs_as(case, torch.float64, absolute=True)
-    q = ladder(case, lambda t_: case.statement(t_, absolute=True), t, lambda v: v.clone(), order, absolute=True)
+    q = absolute_ladder(case, order)
     return max([float(v.abs().max()) for v in q.values() if v is not None and v.numel()] + [0.0])
 
 
@@ -336,11 +395,11 @@ def _add(*a, **kw):
     return c
 
 
-def _conv_inputs(name, fused, lim=3):
-    case = CE.TABLE[name]
+def _conv_inputs(name, fused, lim=3, table=CE.TABLE):
+    case = table[name]
 
     def make():
-        i = CE.integer_inputs(case, lim=lim)
+        i = conv_ints(case, lim=lim)
         x, w, b = i["x"], i["w"], i["bias"]
         if fused:                        # even filter, odd bias: every pre-activation is an odd integer
             w, b = 2.0 * w, 2.0 * b + 1.0
@@ -348,9 +407,13 @@ def _conv_inputs(name, fused, lim=3):
     return make
 
 
-def _conv_cases():
-    for name in CONV_GEOMS:
-        case = CE.TABLE[name]
+def conv_cases(names, direct, _add, table=CE.TABLE):
+    """the rows of the geometries `names` (ConvFn with each activation, its second-order statements) and of `direct` (ConvDgradFn,
+    ConvWgradFn, ConvNoBiasFromGeomFn applied by themselves) through _add; tests/autograd_bf16_cases.py builds its own geometries'
+    rows with it (table: where the geometries are looked up)"""
+    _conv_inputs = lambda name, fused, lim=3: globals()["_conv_inputs"](name, fused, lim, table)
+    for name in names:
+        case = table[name]
         spec = _spec(case)
         for act, tag in ((ACT_NONE, "none"), (ACT_LRELU, "lrelu"), (ACT_RELU, "relu")):
             fused = act != ACT_NONE
@@ -374,23 +437,19 @@ def _conv_cases():
              note="<d y / d w . c, e> to x, w, bias, c: ConvWgradFn.backward")
         _add("conv2:%s:all" % name, cls, _conv_inputs(name, False), ("x", "w", "bias"), stmt, prod, order=2,
              note="every first gradient at once, the bias gradient included")
-    case_a = CE.TABLE["a"]
-    _add("conv3:a", ["ConvFn", "ConvDgradFn", "ConvNoBiasFromGeomFn", "ConvWgradFn"], _conv_inputs("a", False), ("x", "w", "bias"),
-         lambda t, absolute=False: (conv_statement(case_a, t["x"], t["w"], t["bias"]),), lambda F, t: (F.conv(t["x"], t["w"], t["bias"], _spec(case_a)),),
-         order=3, lim=2, note="third-order spot check")
-    for name in ("a", "g"):
-        case = CE.TABLE[name]
+    for name in direct:
+        case = table[name]
 
         def gy_w(case=case):
-            i = CE.integer_inputs(case, lim=3)
+            i = conv_ints(case, lim=3)
             return {"gy": i["gy"], "w": i["w"]}
 
         def x_gy(case=case):
-            i = CE.integer_inputs(case, lim=3)
+            i = conv_ints(case, lim=3)
             return {"x": i["x"], "gy": i["gy"]}
 
         def x_w(case=case):
-            i = CE.integer_inputs(case, lim=3)
+            i = conv_ints(case, lim=3)
             return {"x": i["x"], "w": i["w"]}
         _add("conv_dgrad:%s" % name, ["ConvDgradFn", "ConvNoBiasFromGeomFn", "ConvWgradFn"], gy_w, ("gy", "w"),
              lambda t, absolute=False, case=case: (dgrad_statement(case, t["gy"], t["w"]),),
@@ -401,6 +460,14 @@ def _conv_cases():
         _add("conv_nobias:%s" % name, ["ConvNoBiasFromGeomFn", "ConvDgradFn", "ConvWgradFn"], x_w, ("x", "w"),
              lambda t, absolute=False, case=case: (conv_statement(case, t["x"], t["w"], None),),
              lambda F, t, case=case: (F.ConvNoBiasFromGeomFn.apply(t["x"], t["w"], CE.geom(case)),), order=2)
+
+
+def _conv_cases():
+    conv_cases(CONV_GEOMS, ("a", "g"), _add)
+    case_a = CE.TABLE["a"]
+    _add("conv3:a", ["ConvFn", "ConvDgradFn", "ConvNoBiasFromGeomFn", "ConvWgradFn"], _conv_inputs("a", False), ("x", "w", "bias"),
+         lambda t, absolute=False: (conv_statement(case_a, t["x"], t["w"], t["bias"]),), lambda F, t: (F.conv(t["x"], t["w"], t["bias"], _spec(case_a)),),
+         order=3, lim=2, note="third-order spot check")
 
 
 def _dense_cases():

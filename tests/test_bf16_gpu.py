@@ -9,7 +9,12 @@ Tolerances are stated per test.  A bf16 value carries 8 significant bits (relati
   * whole networks / losses are compared with the fp32-exact oracle on the unrounded weights: every layer rounds its
     output once, so the error grows like sqrt(depth) * 2^-9 relative: 3e-2 of the output scale is asserted for the
     generator image (relative L2; single pixels up to 0.2 of the tanh range) and the loss scalars
-    (scripts/dev/bf16_diag.py prints the layer-by-layer growth)."""
+    (scripts/dev/bf16_diag.py prints the layer-by-layer growth).
+
+The sharp bf16 checks are elsewhere: the kernels bit for bit in tests/test_conv_edges_gpu.py (section 6), tests/test_wgrad_edges_gpu.py,
+tests/test_stream_edges_gpu.py, tests/test_nc_edges_gpu.py and tests/test_filter_prep_gpu.py; the normalisation tails in
+tests/test_norm_tails_gpu.py; and the autograd Functions' forward and backward chains in this mode -- every storage arm of the
+convolution wrappers, the conversions at their edges, the R1 statement -- bit for bit in tests/test_autograd_bf16_gpu.py."""
 import math
 import os
 
