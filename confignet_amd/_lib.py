@@ -72,6 +72,7 @@ SIGNATURES = {
     "cn_conv_dgrad": [_G, _p, _p, _p, _p],
     "cn_conv_dgrad_w": [_G, _p, _p, _p, _p],
     "cn_conv_dgrad_w_res": [_G, _p, _p, _p, _p, _p],
+    "cn_conv_dgrad_w_mask": [_G, _p, _p, _p, _p, _p, _p, _p, _p],
     "cn_bn_fold_bwd_chunks": [],
     "cn_bn_fold_bwd": [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p],
     "cn_conv_wgrad_thin_partials": [],
@@ -93,6 +94,7 @@ SIGNATURES = {
     "cn_gemm_rows_grouped_plan": [_p, _i, ctypes.POINTER(_i), _i, ctypes.POINTER(_i)],
     "cn_conv_tune": [_i, _i, ctypes.c_long],
     "cn_conv_fwd_plan": [_G, _i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int * 8)],
+    "cn_conv_fwd_plan_ep": [_G, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int * 8)],
     "cn_conv_loop_select": [_i, _i, _i, _i],
     "cn_fwd2_col_block": [_i, _i, _i, _i, _i, _i],
     "cn_conv_fwd_dt": [_p, _p, _i, _p, _p, _p, _i, _i, _f, _p],
@@ -101,6 +103,7 @@ SIGNATURES = {
     "cn_conv_wgrad_c3": [_p, _p, _p, _i, _p, _p, _i, _p],
     "cn_conv_wino_filter": [_p, _p, _i, _i, _i, _p],
     "cn_conv_fwd_wino": [_i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _f, _p],
+    "cn_conv_fwd_wino_ep": [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p],
     "cn_conv_fwd_wino4": [_i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _f, _p],
     "cn_conv_fwd_wino4_ep": [_i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _f, _i, _p, _p, _p, _p, _i, _f, _p],
     "cn_conv_wino4_filter": [_p, _p, _i, _i, _i, _p],

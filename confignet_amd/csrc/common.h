@@ -49,10 +49,14 @@ int cn_sum_parts(const float* src, float* dst, int parts, long count, int accumu
 // fwd2.hip: C[M][N] (+)= A[M][K] B for the 1x1 stride-1 convolutions (gp = NULL) and, with a geometry, the same main loop over the
 // gathered rows of a vec convolution (par: parity-ordered rows); tile cfg 0 / 1 / 2 / 3 / 4 of the implicit-GEMM numbering, bt = B is the
 // original filter [N][K] (data gradient), the split-K protocol of igemm_fwd_kernel; both operands go straight into LDS (LDS-DMA), NS
-// stages deep; x_elems / w_elems size the buffer descriptors; CN_EUNSUPPORTED for anything it does not take
+// stages deep; x_elems / w_elems size the buffer descriptors; CN_EUNSUPPORTED for anything it does not take.
+// mask (shaped like C) / colsum / colsum2: the consumer's ReLU backward and its column sums in the epilogue of an unsplit bt launch
+// (cn_conv_dgrad_w_mask); cn_fwd2_takes_mask says which launches carry it
 int cn_fwd2(const CnConvGeom* gp, int cfg, int bt, const float* A, const float* B, const float* bias, float* C, long M, int N, int K,
             int act, float slope, int splits, long part_stride, int par, hipStream_t s, const float* res, double x_elems, double w_elems,
-            float* stats = nullptr, int stats_mode = 0, float stats_slope = 0.f, int srows = 1, int sper = 1);
+            float* stats = nullptr, int stats_mode = 0, float stats_slope = 0.f, int srows = 1, int sper = 1, const float* mask = nullptr,
+            float* colsum = nullptr, float* colsum2 = nullptr);
+bool cn_fwd2_takes_mask(int cfg, int bt, int gathered, int n, int has_bias, int act, int has_stats);
 void cn_fwd2_tune(int kb, int ns, int np);
 void cn_fwd2_grid(int cfg, long M, int N, int par, int splits, int grid[3]);      // the launch grid cn_fwd2 uses
 // igemm_conv.hip: the register-staged implicit-GEMM loop on tile cfg (anything but 0 / 1 / 3 / 4: 64 x 64), the same split-K protocol;

@@ -3,9 +3,10 @@
 // Every fp32 forward / data-gradient convolution is served in two steps: plan_conv_fwd decides the launch from the geometry and
 // the request alone (route, tile, K split, profile family, grid -- no HIP call, no pointer), run_conv_fwd performs it (one switch
 // over the route, one profile bracket, one launch check, the split-K protocol).  cn_conv_fwd_plan reports the plan without a
-// device.  The kernels live in small_conv.hip (thin and image-side layers), fwd2.hip (the LDS-DMA loop) and igemm_conv.hip (the
-// register-staged implicit-GEMM loop).  The filter gradient is served the same way by plan_conv_wgrad / run_conv_wgrad /
-// cn_conv_wgrad_plan in the second half of this file; the tuning hooks are at its end.
+// device (cn_conv_fwd_plan_ep: the same for a request with the mask epilogue of cn_conv_dgrad_w_mask).  The kernels live in
+// small_conv.hip (thin and image-side layers), fwd2.hip (the LDS-DMA loop) and igemm_conv.hip (the register-staged implicit-GEMM
+// loop).  The filter gradient is served the same way by plan_conv_wgrad / run_conv_wgrad / cn_conv_wgrad_plan in the second half
+// of this file; the tuning hooks are at its end.
 #include "common.h"
 
 #include <algorithm>
@@ -26,9 +27,17 @@ constexpr int g_fwd2_min_c = 48;     // thinnest layer it takes
 
 // What the caller asks for, as far as the choice of the launch depends on it.  bt = 1: w is the original filter of the convolution
 // whose data gradient the geometry describes (see igemm_fwd_kernel); stats_mode: cn_conv_fwd_stats; x_dt / y_dt: storage types of
-// input and output (anything but fp32 on both sides: cn_conv_fwd_dt).
+// input and output (anything but fp32 on both sides: cn_conv_fwd_dt); has_mask: the consumer's ReLU backward (and its column sums) in
+// the launch's epilogue (cn_conv_dgrad_w_mask).
 struct ConvReq {
-    int bt, has_bias, act, has_res, stats_mode, x_dt, y_dt;
+    int bt, has_bias, act, has_res, stats_mode, x_dt, y_dt, has_mask = 0;
+};
+
+// The operands of the mask epilogue: the saved activation (shaped like the output) and the destinations of the column sums.
+struct ConvEp {
+    const float* mask = nullptr;
+    float* colsum = nullptr;
+    float* colsum2 = nullptr;
 };
 
 struct ConvPlan {
@@ -63,7 +72,10 @@ int image_route(const CnConvGeom& g, const ConvReq& q) {
 ConvPlan plan_conv_fwd(const CnConvGeom& g, const ConvReq& q) {
     ConvPlan p;
     const long M = (long)g.n * g.out_d * g.out_h * g.out_w;
-    const bool res = q.has_res != 0, stats = q.stats_mode != 0;
+    // a mask request is a residual request to the plan (only an unsplit launch carries either; a split is priced against the pass
+    // that then follows it) that, like the statistics, only the LDS-DMA loop serves
+    const bool mask = q.has_mask != 0;
+    const bool res = q.has_res != 0 || mask, stats = q.stats_mode != 0;
     const int bt = q.bt;
     auto small = [&p](int route, int family, long grid_x) {      // a single launch of a small_conv.hip / thin kernel
         p.route = route;
@@ -81,7 +93,7 @@ ConvPlan plan_conv_fwd(const CnConvGeom& g, const ConvReq& q) {
                                                          : (long)g.n * cn_cdiv(g.out_h, 8) * cn_cdiv(g.out_w, 32);
     const int img_family = img == CN_ROUTE_C3 || img == CN_ROUTE_C7S2 ? CN_FAM_C3_FWD : CN_FAM_S2_IMAGE_DGRAD;
     if (q.x_dt != CN_F32 || q.y_dt != CN_F32)        // mixed storage types: the image-side kernels or nothing
-        return img != CN_ROUTE_UNSUPPORTED ? small(img, img_family, img_grid) : p;
+        return img != CN_ROUTE_UNSUPPORTED && !mask ? small(img, img_family, img_grid) : p;
     // res: only the unsplit implicit-GEMM launches carry the residual add in their epilogue -- anything else answers
     // CN_EUNSUPPORTED before launching (the caller then adds it with a pass of its own)
     if ((res || stats) && (g.cout <= 4 || g.cin == 3 || g.cout % 4 != 0)) return p;
@@ -248,6 +260,10 @@ ConvPlan plan_conv_fwd(const CnConvGeom& g, const ConvReq& q) {
     // 128 x 32 tile on more than 32 channels): igemm_fwd_kernel
     p.route = fwd2_takes && (cfg != 3 || n32) && cfg >= 0 && cfg <= 4 ? CN_ROUTE_FWD2 : CN_ROUTE_IGEMM;
     if (stats && p.route != CN_ROUTE_FWD2) return refuse(CN_EINVAL);      // (a forced tile nobody has: never a kernel without the statistics)
+    if (mask && p.route != CN_ROUTE_FWD2) {          // igemm_fwd_kernel has no mask epilogue: nothing is launched
+        p.route = CN_ROUTE_UNSUPPORTED;
+        return p;
+    }
     p.ret = CN_OK;
     p.cfg = cfg;
     p.splits = splits;
@@ -268,7 +284,7 @@ ConvPlan plan_conv_fwd(const CnConvGeom& g, const ConvReq& q) {
 // Performs the plan: the split-K protocol (zero pass or, in deterministic mode, partial slabs + cn_sum_parts; the bias / activation
 // pass behind a split) around ONE launch.  A plan without a launch returns its code before anything is enqueued.
 int run_conv_fwd(const ConvPlan& p, const CnConvGeom& g, const ConvReq& q, const void* x, const float* w, const float* bias,
-                 const float* res, void* y, float slope, float* stats, float stats_slope, hipStream_t s) {
+                 const float* res, void* y, float slope, float* stats, float stats_slope, hipStream_t s, const ConvEp& ep = ConvEp{}) {
     if (p.route == CN_ROUTE_UNSUPPORTED) return p.ret;
     const long M = (long)g.n * g.out_d * g.out_h * g.out_w;
     const int splits = p.splits;
@@ -283,13 +299,15 @@ int run_conv_fwd(const ConvPlan& p, const CnConvGeom& g, const ConvReq& q, const
     }
     const long part_stride = parts ? (long)M * g.cout : 0;
     float* const out = parts ? parts : (float*)y;
-    if (p.family >= 0) cn_prof_begin(s, conv_flops(g), conv_bytes(g, q.x_dt == CN_BF16 ? 2.0 : 4.0, q.y_dt == CN_BF16 ? 2.0 : 4.0), p.family);
+    const double ep_bytes = ep.mask ? 4.0 * (double)M * g.cout : 0.0;      // (the mask is read once, like the output is written)
+    if (p.family >= 0)
+        cn_prof_begin(s, conv_flops(g), conv_bytes(g, q.x_dt == CN_BF16 ? 2.0 : 4.0, q.y_dt == CN_BF16 ? 2.0 : 4.0) + ep_bytes, p.family);
     int e = CN_OK;
     switch (p.route) {
         case CN_ROUTE_FWD2: {
             const double xe = (double)g.n * g.in_d * g.in_h * g.in_w * g.cin, we = (double)g.k_d * g.k_h * g.k_w * g.cin * g.cout;
             e = cn_fwd2(p.plain ? nullptr : &g, p.cfg, q.bt, (const float*)x, w, bias, out, M, g.cout, g.cin, kact, slope, splits, part_stride,
-                        p.plain ? 0 : p.par, s, res, xe, we, stats, q.stats_mode, stats_slope, p.srows, p.sper);
+                        p.plain ? 0 : p.par, s, res, xe, we, stats, q.stats_mode, stats_slope, p.srows, p.sper, ep.mask, ep.colsum, ep.colsum2);
             break;
         }
         case CN_ROUTE_IGEMM:
@@ -393,12 +411,46 @@ extern "C" int cn_conv_dgrad_w_res(const CnConvGeom* gp, const float* gy, const 
     return conv_fwd(&d, ConvReq{1, 0, CN_ACT_NONE, 1, 0, CN_F32, CN_F32}, gy, w, nullptr, res, gu, 0.f, nullptr, 0.f, stream);
 }
 
+// cn_conv_dgrad_w[_res] with the ReLU backward of the layer in front in the launch's epilogue (include/confignet_hip.h):
+//     gu = (data gradient (+ res)) * (mask > 0),   colsum[c] += sum_rows gu[.][c],   colsum2[c] += the same
+// -- the bits cn_conv_dgrad_w[_res] followed by cn_act_bwd(.., mask, CN_ACT_RELU) stores, and the shift sums cn_act_bwd_bias would
+// take in a pass of its own (a ResNet block's shortcut convolution receives the sums of its last convolution: colsum2).  res, colsum
+// and colsum2 may be NULL.  Served by the unsplit launches of the LDS-DMA loop on 32-wide blocks, stride 1, no upsampling;
+// everything else -- and any request for sums in deterministic mode, whose order of additions the atomics do not fix --
+// CN_EUNSUPPORTED with nothing enqueued: the caller then runs the data gradient and the pass.
+extern "C" int cn_conv_dgrad_w_mask(const CnConvGeom* gp, const float* gy, const float* w, const float* res, const float* mask, float* gu,
+                                    float* colsum, float* colsum2, void* stream) {
+    if (int e = check_geom(gp)) return e;
+    CN_CHECK_ARG(gy && w && mask && gu, "cn_conv_dgrad_w_mask: NULL tensor");
+    if (gp->dl_d != 1 || gp->dl_h != 1 || gp->dl_w != 1 || gp->up) return CN_EUNSUPPORTED;
+    if (gp->s_d != 1 || gp->s_h != 1 || gp->s_w != 1) return CN_EUNSUPPORTED;      // (parity-ordered rows: as cn_conv_dgrad_w_res)
+    if ((colsum || colsum2) && cn_det()) return CN_EUNSUPPORTED;
+    const CnConvGeom d = dgrad_geom(*gp);
+    const ConvReq q{1, 0, CN_ACT_NONE, res != nullptr, 0, CN_F32, CN_F32, 1};
+    const ConvPlan p = plan_conv_fwd(d, q);
+    if (p.route == CN_ROUTE_UNSUPPORTED) return p.ret;
+    // (what the plan does not know: a tile forced by cn_conv_tune that has no mask instance, the 16-wide-block body at 48 channels)
+    if (p.splits > 1 || !cn_fwd2_takes_mask(p.cfg, 1, !p.plain, d.cout, 0, CN_ACT_NONE, 0)) return CN_EUNSUPPORTED;
+    return run_conv_fwd(p, d, q, gy, w, nullptr, res, gu, 0.f, nullptr, 0.f, (hipStream_t)stream, ConvEp{mask, colsum, colsum2});
+}
+
 // Diagnostic (include/confignet_hip.h): the launch a request WOULD get -- needs no device, enqueues nothing.
 extern "C" int cn_conv_fwd_plan(const CnConvGeom* gp, int bt, int has_bias, int act, int has_res, int stats_mode, int x_dt, int y_dt,
                                 int out[8]) {
     if (int e = check_geom(gp)) return e;
     CN_CHECK_ARG(out, "cn_conv_fwd_plan: out is NULL");
     const ConvPlan p = plan_conv_fwd(*gp, ConvReq{bt, has_bias, act, has_res, stats_mode, x_dt, y_dt});
+    const int v[8] = {p.route, p.cfg, p.splits, p.par, p.family, p.grid[0], p.grid[1], p.grid[2]};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return p.ret;
+}
+
+// cn_conv_fwd_plan for a request with the mask epilogue (has_mask = 0: cn_conv_fwd_plan itself).
+extern "C" int cn_conv_fwd_plan_ep(const CnConvGeom* gp, int bt, int has_bias, int act, int has_res, int stats_mode, int has_mask, int x_dt,
+                                   int y_dt, int out[8]) {
+    if (int e = check_geom(gp)) return e;
+    CN_CHECK_ARG(out, "cn_conv_fwd_plan_ep: out is NULL");
+    const ConvPlan p = plan_conv_fwd(*gp, ConvReq{bt, has_bias, act, has_res, stats_mode, x_dt, y_dt, has_mask != 0});
     const int v[8] = {p.route, p.cfg, p.splits, p.par, p.family, p.grid[0], p.grid[1], p.grid[2]};
     for (int i = 0; i < 8; ++i) out[i] = v[i];
     return p.ret;

@@ -27,6 +27,9 @@
 // The operand reads are inline asm with hand-counted lgkmcnt and the barrier is the bare s_barrier, for the two compiler
 // reasons stated in wgrad2.hip (a ds_read that may alias an LDS-DMA destination is preceded by vmcnt(0); __syncthreads drains
 // the LDS-DMA queue).  scripts/isa_lds_hazard.py replays the compiled loop (tests/test_abi_cpu.py).
+//
+// Epilogues besides bias / activation / residual: the statistics of the following normalisation layer (forward, unsplit), and for
+// the data gradient the ReLU backward of the layer in front with its shift sums (fwd2_mask_kernel; cn_conv_dgrad_w_mask).
 #include "common.h"
 #include "mma_tile.h"
 #include "conv_geom.h"
@@ -88,13 +91,19 @@ __device__ __forceinline__ void f2_static_for(F&& f) {
 // 48 .. 63.  Lane l reads row l & 15, logical piece l >> 4 of a stage row (16 consecutive rows of one piece: the conflict-free
 // pattern again); component c of that ds_read_b128 feeds the c-th MFMA of the stage (k = 4 (l >> 4) + c: A and B permute K alike),
 // so ONE operand set covers the whole 16-deep stage and a step is 4 reads and 4 TM TN MFMAs of 32 cycles.
-template <int WM, int WN, int TM, int TN, bool BT, bool GATHER, int KB, int NS, int NP, bool BF, int CB = 32>
+// MASK: the data gradient's consumer in the epilogue (fp32, BT, 32-wide blocks, unsplit, no bias / activation): the stored value is
+// cn_act_bwd's ReLU rule on v (+ res) with mask[row][col] -- the saved activation, shaped like C -- as the activation output, and its
+// column sums over all rows are added to colsum / colsum2 (either may be NULL; zeroed or accumulated into by the caller).
+template <int WM, int WN, int TM, int TN, bool BT, bool GATHER, int KB, int NS, int NP, bool BF, int CB = 32, bool MASK = false>
 __device__ __forceinline__ void fwd2_body(const CnConvGeom& g, const float* __restrict__ A, const float* __restrict__ B,
                                           const float* __restrict__ bias, float* __restrict__ C, int M, int N, int K,
                                           int act, float slope, int ntm, int ntn, long part_stride, int par,
                                           const float* __restrict__ res, unsigned a_bytes, unsigned b_bytes, int flip,
-                                          float* __restrict__ stats, int stats_mode, float stats_slope, int srows, int sper) {
+                                          float* __restrict__ stats, int stats_mode, float stats_slope, int srows, int sper,
+                                          const float* __restrict__ mask = nullptr, float* __restrict__ colsum = nullptr,
+                                          float* __restrict__ colsum2 = nullptr) {
     static_assert(!BF || BT, "bf16: both operands are K-contiguous rows");
+    static_assert(!MASK || (BT && !BF && CB == 32 && NP == 0), "mask epilogue: the fp32 B^T form on 32-wide blocks");
     constexpr int ES = BF ? 2 : 4;                   // bytes per element
     constexpr int KE = KB * 4 / ES;                  // elements of the reduction axis per stage
     static_assert(WM * WN == 4, "4 waves per workgroup");
@@ -574,6 +583,63 @@ __device__ __forceinline__ void fwd2_body(const CnConvGeom& g, const float* __re
         }
         return;
     }
+    if constexpr (MASK) {
+        // mask epilogue (C/D layout as below; the launch is unsplit): v (+ res), then cn_act_bwd's rule -- the same two operations
+        // on the same operands as the launch without it followed by cn_act_bwd, hence the same bits.  Column sums of the stored
+        // values: the two half-waves (the two row halves of the same columns), then the WM waves that share columns through the
+        // operand stages (free once every wave is past its last read and every LDS-DMA has landed: the barrier), in wave order;
+        // then one add per column and workgroup.
+        float csum[TN];
+#pragma unroll
+        for (int j = 0; j < TN; ++j) csum[j] = 0.f;
+        // The 16 mask (and residual) values of a 32 x 32 block are fetched in one batch before any of them is used -- from element 0
+        // where the row or the column lies outside, so that no load sits behind a branch: fetched where they are used, each of the
+        // 16 waits out its own memory latency at the end of a workgroup that has nothing else to run (+7 us on a 22 us launch).
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int col = n0 + wn * 32 * TN + 32 * j + l31;
+                long o[16];
+                float mk[16], rv[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int lrow = wm * 32 * TM + 32 * i + 4 * half + (r & 3) + 8 * (r >> 2);
+                    const int row = GATHER ? rowmap[lrow] : m0 + lrow;
+                    o[r] = (row >= 0 && row < M && col < N) ? (long)row * N + col : -1;
+                    const long oo = o[r] < 0 ? 0 : o[r];
+                    mk[r] = mask[oo];
+                    rv[r] = res ? res[oo] : 0.f;
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    if (o[r] < 0) continue;
+                    const float v = acc[i][j][r] + 0.f;          // (the launch without the mask adds its absent bias as 0.f: -0.0 becomes +0.0)
+                    const float vr = res ? v + rv[r] : v;
+                    const float a = vr * act_deriv(mk[r], CN_ACT_RELU, 0.f);
+                    C[o[r]] = a;
+                    csum[j] += a;
+                }
+            }
+        if (colsum || colsum2) {
+            static_assert(WM * BN <= NS * (SA + SB) && BN <= 256, "the column sums fit the operand stages, a thread per column");
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const float t = csum[j] + __shfl_xor(csum[j], 32);
+                if (half == 0) SM[wm * BN + wn * 32 * TN + 32 * j + l31] = t;
+            }
+            __syncthreads();
+            if (tid < BN && n0 + tid < N) {
+                float t = SM[tid];
+#pragma unroll
+                for (int w_ = 1; w_ < WM; ++w_) t += SM[w_ * BN + tid];
+                if (colsum) unsafeAtomicAdd(colsum + n0 + tid, t);
+                if (colsum2) unsafeAtomicAdd(colsum2 + n0 + tid, t);
+            }
+        }
+        return;
+    }
     // epilogue: C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
     // stats (unsplit forward launches whose tiles lie inside one sample; reference building_blocks.py:37-44,97-106): the
     // per-(sample, channel) sums the FOLLOWING normalisation layer needs, taken from the values this epilogue holds anyway instead
@@ -675,6 +741,18 @@ __global__ __launch_bounds__(256) void fwd2_n48_kernel(CnConvGeom g, const float
                                                             b_bytes, flip, nullptr, 0, 0.f, 1, 1);
 }
 
+// The data gradient with its consumer's ReLU backward in the epilogue (fwd2_body: MASK): the B^T form on the default loop (16-deep
+// stages, four of them, no loader waves), unsplit, in the place of fwd2_kernel's body in the same launch and grid.
+template <int WM, int WN, int TM, int TN, bool GATHER>
+__global__ __launch_bounds__(256) void fwd2_mask_kernel(CnConvGeom g, const float* __restrict__ A, const float* __restrict__ B,
+                                                        float* __restrict__ C, int M, int N, int K, int ntm, int ntn, int par,
+                                                        const float* __restrict__ res, unsigned a_bytes, unsigned b_bytes,
+                                                        const float* __restrict__ mask, float* __restrict__ colsum,
+                                                        float* __restrict__ colsum2) {
+    fwd2_body<WM, WN, TM, TN, true, GATHER, 16, 4, 0, false, 32, true>(g, A, B, nullptr, C, M, N, K, CN_ACT_NONE, 0.f, ntm, ntn, 0, par, res,
+                                                                       a_bytes, b_bytes, 1, nullptr, 0, 0.f, 1, 1, mask, colsum, colsum2);
+}
+
 // one workgroup per (M tile, N tile): whole rounds of the eight XCDs unless the rows are parity-ordered
 inline unsigned fwd2_grid_x(int ntm, int ntn, int par) { return (unsigned)(par ? ntm * ntn : 8 * cn_cdiv((long)ntm * ntn, 8)); }
 
@@ -698,6 +776,23 @@ int launch2(const CnConvGeom& g, const float* A, const float* B, const float* bi
     dim3 grid(fwd2_grid_x(ntm, ntn, par), 1, (unsigned)splits);
     hipLaunchKernelGGL((fwd2_kernel<WM, WN, TM, TN, BT, GATHER, KB, NS, NP, BF>), grid, dim3(256 + 64 * NP), 0, s, g, A, B, bias, C, (int)M, N, K, act,
                        slope, ntm, ntn, part_stride, par, res, a_bytes, b_bytes, flip, stats, stats_mode, stats_slope, srows, sper);
+    CN_LAUNCH_CHECK();
+    return CN_OK;
+}
+
+template <int WM, int WN, int TM, int TN>
+int launch2_mask(const CnConvGeom* gp, const float* A, const float* B, float* C, long M, int N, int K, int par, hipStream_t s, const float* res,
+                 unsigned a_bytes, unsigned b_bytes, const float* mask, float* colsum, float* colsum2) {
+    constexpr int BM = 32 * WM * TM, BN = 32 * WN * TN;
+    static const CnConvGeom none = {};
+    const int ntm = cn_cdiv(M, BM), ntn = cn_cdiv(N, BN);
+    const dim3 grid(fwd2_grid_x(ntm, ntn, gp ? par : 0));
+    if (gp)
+        hipLaunchKernelGGL((fwd2_mask_kernel<WM, WN, TM, TN, true>), grid, dim3(256), 0, s, *gp, A, B, C, (int)M, N, K, ntm, ntn, par, res, a_bytes,
+                           b_bytes, mask, colsum, colsum2);
+    else
+        hipLaunchKernelGGL((fwd2_mask_kernel<WM, WN, TM, TN, false>), grid, dim3(256), 0, s, none, A, B, C, (int)M, N, K, ntm, ntn, 0, res, a_bytes,
+                           b_bytes, mask, colsum, colsum2);
     CN_LAUNCH_CHECK();
     return CN_OK;
 }
@@ -727,18 +822,34 @@ extern "C" int cn_fwd2_col_block(int cfg, int bt, int gathered, int n, int kb, i
     return (cfg == 2 && bt && gathered && n == 48 && kb == 16 && np == 0) ? 16 : 32;
 }
 
+// Whether a cn_fwd2 launch can carry the mask epilogue (fwd2_mask_kernel): the data-gradient form (bt) without bias, activation or
+// statistics, on the 64 x 64, 128 x 32 or 128 x 96 tile -- the tiles plan_conv_fwd gives this loop -- and not the 16-wide-block body
+// that takes the 64 x 64 tile's place at 48 output channels.  Such a launch always runs the default loop (cn_fwd2_tune is not asked).
+bool cn_fwd2_takes_mask(int cfg, int bt, int gathered, int n, int has_bias, int act, int has_stats) {
+    return bt && !has_bias && act == CN_ACT_NONE && !has_stats && (cfg == 2 || cfg == 3 || cfg == 4) &&
+           cn_fwd2_col_block(cfg, bt, gathered, n, 16, 0) == 32;
+}
+
 // The contract stated in common.h: tile cfg 0 / 1 / 2 / 4, bt = B is the original filter [N][K] (data gradient), split-K
 // protocol of igemm_fwd_kernel, gp = NULL for the plain 1x1 stride-1 product, else the geometry whose gather builds the rows (par:
 // parity-ordered).  x_elems / w_elems: sizes of the two tensors (the buffer descriptors' ranges).
 int cn_fwd2(const CnConvGeom* gp, int cfg, int bt, const float* A, const float* B, const float* bias, float* C, long M, int N, int K,
             int act, float slope, int splits, long part_stride, int par, hipStream_t s, const float* res, double x_elems, double w_elems,
-            float* stats, int stats_mode, float stats_slope, int srows, int sper) {
-    if ((res || stats) && (splits > 1 || part_stride)) return CN_EUNSUPPORTED;
+            float* stats, int stats_mode, float stats_slope, int srows, int sper, const float* mask, float* colsum, float* colsum2) {
+    if ((res || stats || mask) && (splits > 1 || part_stride)) return CN_EUNSUPPORTED;
     if (stats && bt) return CN_EUNSUPPORTED;
+    if ((colsum || colsum2) && !mask) return CN_EUNSUPPORTED;
+    if (mask && !cn_fwd2_takes_mask(cfg, bt, gp != nullptr, N, bias != nullptr, act, stats != nullptr)) return CN_EUNSUPPORTED;
     if (K % 16 != 0 || N % 4 != 0 || M <= 0 || M > 0x7fffffffL || (par && !gp)) return CN_EUNSUPPORTED;
     if (gp && (gp->dl_d > 2 || gp->dl_h > 2 || gp->dl_w > 2)) return CN_EUNSUPPORTED;     // (the gather's shift-and-mask form)
     if (x_elems * 4.0 >= 2147483647.0 || w_elems * 4.0 >= 2147483647.0) return CN_EUNSUPPORTED;      // 32-bit byte offsets
     const unsigned ab = (unsigned)(x_elems * 4.0), bb = (unsigned)(w_elems * 4.0);
+    if (mask) {
+        const int mpar = gp ? par : 0;
+        if (cfg == 2) return launch2_mask<2, 2, 1, 1>(gp, A, B, C, M, N, K, mpar, s, res, ab, bb, mask, colsum, colsum2);
+        if (cfg == 3) return launch2_mask<4, 1, 1, 1>(gp, A, B, C, M, N, K, mpar, s, res, ab, bb, mask, colsum, colsum2);
+        return launch2_mask<4, 1, 1, 3>(gp, A, B, C, M, N, K, mpar, s, res, ab, bb, mask, colsum, colsum2);
+    }
     static const CnConvGeom none = {};
     // Loop variant.  Defaults: 16-deep stages, FOUR stages, no loader waves.  How they were arrived at (all three are decided by
     // alternating bench.py runs on one box, scripts/dev/pipe_ab.sh -- isolated timings of one shape say something else for each):

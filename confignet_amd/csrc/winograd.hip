@@ -13,6 +13,8 @@
 // pair) (8-byte loads, 4 lanes = one 32-byte sector), transforms it in registers and writes the 16 V planes to LDS
 // (k-major, like igemm_conv.hip); the filter U[p][ci][co] is transformed once per weight update (cn_conv_wino_filter).
 // A step is 64 MFMAs per wave (4096 cycles): the next step's global loads are issued before them and have that long to land.
+// The data-gradient launch can carry the ReLU backward of the layer in front and its shift sums in the output loop
+// (wino_fwd_kernel<true>; cn_conv_fwd_wino_ep).
 #include "common.h"
 
 #include "mma_tile.h"
@@ -59,8 +61,14 @@ __global__ void wino_filter_kernel(const float* __restrict__ W, float* __restric
     }
 }
 
+// EP (data gradient; launches without it keep their instruction text): the ReLU backward of the layer in front in the output loop --
+// the stored value is cn_act_bwd's rule on the finished pixel with mask (shaped like Y, read at the address the pixel is stored to) as
+// the activation output, and the column sums of the stored values are added to colsum / colsum2 (either may be NULL).
+template <bool EP>
 __global__ __launch_bounds__(512, 1) void wino_fwd_kernel(WinoGeom g, const float* __restrict__ X, const float* __restrict__ U,
-                                                          const float* __restrict__ bias, float* __restrict__ Y, int act, float slope) {
+                                                          const float* __restrict__ bias, float* __restrict__ Y, int act, float slope,
+                                                          const float* __restrict__ mask, float* __restrict__ colsum,
+                                                          float* __restrict__ colsum2) {
     constexpr int BT = 64, BC = 64, LDV = BT + 4, LDU = BC;
     constexpr int RAW_SLOTS = 324, RAW_FLOATS = 12 * 64 * 4;    // 18 x 18 pixels x 8 channels, rounded up to 12 wave loads
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -245,9 +253,26 @@ __global__ __launch_bounds__(512, 1) void wino_fwd_kernel(WinoGeom g, const floa
             }
         }
     }
-    __syncthreads();
     const int co = c0 + wc * 32 + l31;
+    // EP: the 32 mask values of this lane's pixels, fetched in one batch in front of the barrier (the accumulators are dead by now) --
+    // from element co where the pixel lies outside the image, so that no load sits behind a branch: fetched where they are used, each
+    // waits out its own memory latency in a workgroup that has the CU to itself (+17 us on a 56 us launch).
+    float mk[EP ? 16 : 1][2];
+    if constexpr (EP) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int tl = wt * 32 + 4 * half + (r & 3) + 8 * (r >> 2);
+            const int base = tilebase[tl];
+            const int hw = tilehw[tl], oy = hw >> 16, ox = hw & 0xffff;
+            const bool in0 = base >= 0 && oy + ph < g.h, in1 = in0 && ox + 1 < g.w;
+            const long o = ((long)base + ph * g.w) * g.cout + co;
+            mk[r][0] = mask[in0 ? o : (long)co];
+            mk[r][1] = mask[in1 ? o + g.cout : (long)co];
+        }
+    }
+    __syncthreads();
     const float bv = bias ? bias[co] : 0.f;
+    float cs = 0.f;                              // EP: this lane's part of column co's sum
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int tl = wt * 32 + 4 * half + (r & 3) + 8 * (r >> 2);
@@ -256,9 +281,38 @@ __global__ __launch_bounds__(512, 1) void wino_fwd_kernel(WinoGeom g, const floa
         const float y0 = keep[r][0] + xchg[(((ph ^ 1) * 16 + r) * 2 + 0) * 64 + lane];
         const float y1 = keep[r][1] + xchg[(((ph ^ 1) * 16 + r) * 2 + 1) * 64 + lane];
         if (base < 0 || oy + ph >= g.h) continue;
-        float* dst = Y + ((long)base + ph * g.w) * g.cout + co;
-        dst[0] = cn_apply_act(y0 + bv, act, slope);
-        if (ox + 1 < g.w) dst[g.cout] = cn_apply_act(y1 + bv, act, slope);
+        const long o = ((long)base + ph * g.w) * g.cout + co;
+        float* dst = Y + o;
+        if constexpr (EP) {
+            // (the same operations on the same operands as the launch without EP followed by cn_act_bwd: the same bits)
+            const float a0 = cn_apply_act(y0 + bv, act, slope) * act_deriv(mk[r][0], CN_ACT_RELU, 0.f);
+            dst[0] = a0;
+            cs += a0;
+            if (ox + 1 < g.w) {
+                const float a1 = cn_apply_act(y1 + bv, act, slope) * act_deriv(mk[r][1], CN_ACT_RELU, 0.f);
+                dst[g.cout] = a1;
+                cs += a1;
+            }
+        } else {
+            dst[0] = cn_apply_act(y0 + bv, act, slope);
+            if (ox + 1 < g.w) dst[g.cout] = cn_apply_act(y1 + bv, act, slope);
+        }
+    }
+    if constexpr (EP) {
+        // column sums of the workgroup (64 tiles x 64 channels): the two half-waves, then the four waves (output row ph, tile half wt)
+        // that share a column through the operand buffers behind the exchange area (no longer read by anybody: the barrier in front
+        // of the output transform), in wave order; then one add per column and workgroup
+        if (colsum || colsum2) {
+            float* red = smem + 4 * 2 * 16 * 2 * 64;     // [ph * 2 + wt][64]
+            const float t = cs + __shfl_xor(cs, 32);
+            if (half == 0) red[(ph * 2 + wt) * 64 + wc * 32 + l31] = t;
+            __syncthreads();
+            if (tid < 64) {
+                const float s_ = ((red[tid] + red[64 + tid]) + red[128 + tid]) + red[192 + tid];
+                if (colsum) unsafeAtomicAdd(colsum + c0 + tid, s_);
+                if (colsum2) unsafeAtomicAdd(colsum2 + c0 + tid, s_);
+            }
+        }
     }
 }
 
@@ -273,27 +327,51 @@ extern "C" int cn_conv_wino_filter(const float* w, float* u, int cin, int cout, 
     return CN_OK;
 }
 
+namespace {
+
+// the one launch of wino_fwd_kernel (EP: with the mask epilogue)
+template <bool EP>
+int wino_launch(int n, int h, int w, int cin, int cout, const float* x, const float* u, const float* bias, float* y, int act, float slope,
+                const float* mask, float* colsum, float* colsum2, void* stream) {
+    CN_CHECK_ARG((double)n * h * w * (cin > cout ? cin : cout) * 4.0 < 2147483647.0 && 64.0 * cin * cout < 2147483647.0, "tensor exceeds 2^31 bytes (buffer descriptors, 32-bit offsets)");
+    WinoGeom g{n, h, w, cin, cout, (h + 1) / 2, (w + 1) / 2, (h + 15) / 16, (w + 15) / 16};
+    const long ntiles = (long)n * g.th * g.tw, nblk = (long)n * g.bh * g.bw;
+    constexpr size_t lds = sizeof(float) * (2 * 16 * WKB * (68 + 64)) + sizeof(int) * 128;     // + 24 KB static (input blocks)
+    static bool attr_set = false;                    // (one per instantiation)
+    if (!attr_set) {
+        CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(wino_fwd_kernel<EP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        attr_set = true;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    // MFMA work that contributes to the result: 16 products per 2x2 output tile and (ci, co) pair; EP: the mask is read once
+    cn_prof_begin(s, 2.0 * 16.0 * (double)ntiles * cin * cout,
+                  4.0 * ((double)n * h * w * (cin + cout * (EP ? 2 : 1)) + 16.0 * cin * cout), CN_FAM_WINO);
+    hipLaunchKernelGGL(wino_fwd_kernel<EP>, dim3((unsigned)(nblk * (cout / 64))), dim3(512), lds, s, g, x, u, bias, y, act, slope, mask, colsum,
+                       colsum2);
+    cn_prof_end(s);
+    CN_LAUNCH_CHECK();
+    return CN_OK;
+}
+
+}  // namespace
+
 // x (n, h, w, cin) -> y (n, h, w, cout): 3x3, stride 1, SAME; u from cn_conv_wino_filter ([16][cin][cout]).
 // Returns CN_EUNSUPPORTED (nothing launched) unless cin % 16 == 0 and cout % 64 == 0.
 extern "C" int cn_conv_fwd_wino(int n, int h, int w, int cin, int cout, const float* x, const float* u, const float* bias,
                                 float* y, int act, float slope, void* stream) {
     CN_CHECK_ARG(x && u && y && n > 0 && h > 0 && w > 0, "conv_fwd_wino: bad args");
     if (cin % (2 * WKB) || cout % 64) return CN_EUNSUPPORTED;
-    CN_CHECK_ARG((double)n * h * w * (cin > cout ? cin : cout) * 4.0 < 2147483647.0 && 64.0 * cin * cout < 2147483647.0, "tensor exceeds 2^31 bytes (buffer descriptors, 32-bit offsets)");
-    WinoGeom g{n, h, w, cin, cout, (h + 1) / 2, (w + 1) / 2, (h + 15) / 16, (w + 15) / 16};
-    const long ntiles = (long)n * g.th * g.tw, nblk = (long)n * g.bh * g.bw;
-    constexpr size_t lds = sizeof(float) * (2 * 16 * WKB * (68 + 64)) + sizeof(int) * 128;     // + 24 KB static (input blocks)
-    static bool attr_set = false;
-    if (!attr_set) {
-        CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(wino_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    // MFMA work that contributes to the result: 16 products per 2x2 output tile and (ci, co) pair
-    cn_prof_begin(s, 2.0 * 16.0 * (double)ntiles * cin * cout,
-                  4.0 * ((double)n * h * w * (cin + cout) + 16.0 * cin * cout), CN_FAM_WINO);
-    hipLaunchKernelGGL(wino_fwd_kernel, dim3((unsigned)(nblk * (cout / 64))), dim3(512), lds, s, g, x, u, bias, y, act, slope);
-    cn_prof_end(s);
-    CN_LAUNCH_CHECK();
-    return CN_OK;
+    return wino_launch<false>(n, h, w, cin, cout, x, u, bias, y, act, slope, nullptr, nullptr, nullptr, stream);
+}
+
+// The data-gradient launch (u = the dgrad filter, no bias, no activation) with the ReLU backward of the layer in front in its output
+// loop (include/confignet_hip.h): y = conv * (mask > 0), bit for bit cn_conv_fwd_wino followed by cn_act_bwd(y, mask, CN_ACT_RELU), and
+// colsum[c] / colsum2[c] += the column sums of y (either may be NULL).  CN_EUNSUPPORTED (nothing launched) as cn_conv_fwd_wino, and
+// for a request with sums in deterministic mode (the atomics fix no order of additions).
+extern "C" int cn_conv_fwd_wino_ep(int n, int h, int w, int cin, int cout, const float* x, const float* u, float* y, const float* mask,
+                                   float* colsum, float* colsum2, void* stream) {
+    CN_CHECK_ARG(x && u && y && mask && n > 0 && h > 0 && w > 0, "conv_fwd_wino_ep: bad args");
+    if (cin % (2 * WKB) || cout % 64) return CN_EUNSUPPORTED;
+    if ((colsum || colsum2) && cn_det()) return CN_EUNSUPPORTED;
+    return wino_launch<true>(n, h, w, cin, cout, x, u, nullptr, y, CN_ACT_NONE, 0.f, mask, colsum, colsum2, stream);
 }

@@ -231,6 +231,7 @@ class RealEncoder(Net):
         return [w for w in self.weights[:-4] if w.requires_grad]
 
     folded_tape = True         # (False: the taped form as convolution + per-channel affine pass per layer -- cross-check)
+    fused_relu_bwd = True      # (False: the trunk's backward with a ReLU-backward pass behind every data gradient -- cross-check, A/B)
 
     def _conv_bn(self, ci, x, coef, res=None, relu=True):
         kidx, _, spec = self._convs[ci]
@@ -291,9 +292,11 @@ class ResNetTrunkFn(torch.autograd.Function):
     (round 6).  BatchNormalization runs in inference mode (R9), so  relu(bn(conv(x, w) + b) [+ shortcut])  is
     relu(conv(x, w a) + shift [+ shortcut])  with a = gamma rsqrt(var + eps), shift = beta + a (b - mean): one launch per
     layer with bias / residual / ReLU in its epilogue -- the form the tape-free encoder has used since round 4 -- instead of a
-    convolution plus a per-channel affine pass over its output.  Backward per layer: ReLU mask + shift sums in one pass
-    (cn_act_bwd_bias), data gradient (a block's skip gradient added in the epilogue of its first convolution's data gradient,
-    cn_conv_dgrad_w_res, instead of by autograd's add), filter gradient WRITTEN into a packed scratch -- not between two data
+    convolution plus a per-channel affine pass over its output.  Backward per layer: data gradient (a block's skip gradient added
+    in the epilogue of its first convolution's data gradient instead of by autograd's add) with the ReLU mask and the shift sums
+    of the layer in front in the same epilogue (ops.conv_dgrad_mask: cn_conv_dgrad_w_mask / cn_conv_fwd_wino_ep; where the launch
+    does not carry them -- a K split, deterministic mode, RealEncoder.fused_relu_bwd = False -- cn_conv_dgrad_w[_res] and one
+    pass, cn_act_bwd_bias), filter gradient WRITTEN into a packed scratch -- not between two data
     gradients, which alone feed the chain, but recorded and issued for all layers in a few grouped launches at the end of the
     pass (cn_conv_wgrad_grouped; the cotangents stay alive until then: 409 MB at n = 8, 818 MB at n = 16); the gradients of
     kernel / bias / gamma / beta of all 53 pairs then come out of ONE launch at the join of the pass (cn_bn_fold_bwd):
@@ -400,24 +403,47 @@ class ResNetTrunkFn(torch.autograd.Function):
             for bi in range(blocks_):
                 layout.append((ci, bi == 0))
                 ci += 4 if bi == 0 else 3
+        fused = enc.fused_relu_bwd
+
+        def dgrad_relu(gy_, ci_w, t_in_, y, cis, res=None):
+            """The data gradient of layer ci_w (+ res) with the ReLU backward of the layer whose output y is in its epilogue, the
+            shift sums into the layers `cis` (ops.conv_dgrad_mask: one launch where the launch carries it)."""
+            sums = [gsh[offs[c]:offs[c + 1]] for c in cis if c is not None] if want_w else []
+            return ops.conv_dgrad_mask(gy_, wf[ci_w], geom(ci_w, t_in_), y, res=res, sums=sums, defer=sunk)
+
         pos = len(saved)
-        for first, has_sc in reversed(layout):
+        masked = False                               # fused walk: g arrives with the ReLU backward of the block's output applied
+        for k in range(len(layout) - 1, -1, -1):
+            first, has_sc = layout[k]
             y1, y2, t_out = saved[pos - 3], saved[pos - 2], saved[pos - 1]
             pos -= 3
             t_in = saved[pos - 1]
             c1 = first + 1 if has_sc else first
-            gu3 = relu_bwd(c1 + 2, g, t_out, also=first if has_sc else None)
+            gu3 = g if masked else relu_bwd(c1 + 2, g, t_out, also=first if has_sc else None)
             wgrad(c1 + 2, y2, gu3)
-            gu2 = relu_bwd(c1 + 1, ops.conv_dgrad(gu3, wf[c1 + 2], geom(c1 + 2, y2)), y2)
+            if fused:
+                gu2 = dgrad_relu(gu3, c1 + 2, y2, y2, (c1 + 1,))
+            else:
+                gu2 = relu_bwd(c1 + 1, ops.conv_dgrad(gu3, wf[c1 + 2], geom(c1 + 2, y2)), y2)
             wgrad(c1 + 1, y1, gu2)
-            gu1 = relu_bwd(c1, ops.conv_dgrad(gu2, wf[c1 + 1], geom(c1 + 1, y1)), y1)
+            if fused:
+                gu1 = dgrad_relu(gu2, c1 + 1, y1, y1, (c1,))
+            else:
+                gu1 = relu_bwd(c1, ops.conv_dgrad(gu2, wf[c1 + 1], geom(c1 + 1, y1)), y1)
             wgrad(c1, t_in, gu1)
             if has_sc:
                 wgrad(first, t_in, gu3)
                 skip = ops.conv_dgrad(gu3, wf[first], geom(first, t_in))
             else:
                 skip = gu3
-            g = ops.conv_dgrad_res(gu1, wf[c1], geom(c1, t_in), skip)
+            masked = fused and k > 0
+            if masked:
+                # t_in is the output of block k - 1: its ReLU backward (the sums go to that block's last convolution and to its
+                # shortcut convolution) rides in this launch
+                pfirst, psc = layout[k - 1]
+                g = dgrad_relu(gu1, c1, t_in, t_in, ((pfirst + 1 if psc else pfirst) + 2, pfirst if psc else None), res=skip)
+            else:
+                g = ops.conv_dgrad_res(gu1, wf[c1], geom(c1, t_in), skip)
         x, y0, t = saved[0], saved[1], saved[2]
         g = ops.maxpool_bwd(y0, g, 3, 2, 1)
         gu0 = relu_bwd(0, g, y0)

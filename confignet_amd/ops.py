@@ -581,6 +581,62 @@ def conv_dgrad_res(gy, w, g, res):
     return nc_lin2(tuple(gu.shape), gu, None, res, None, None)
 
 
+MASK_EPILOGUE = True           # conv_dgrad_mask: False = always the data gradient and the pass
+MASK_LOG = None                # a list (tests, A/B): conv_dgrad_mask appends "fwd2" / "wino" / "pass" per call
+
+
+def conv_dgrad_mask(gy, w, g, mask, res=None, sums=(), defer=True):
+    """act_bwd(conv_dgrad(gy, w, g) [+ res], mask, ACT_RELU) and, for every slice in `sums` (at most two), slice[c] += the channel
+    sums of the result: the ReLU backward of the layer in front and its shift sums in the data-gradient launch's epilogue where
+    the launch carries them -- Winograd F(2x2) where conv_dgrad takes it and there is no residual (cn_conv_fwd_wino_ep), else the
+    unsplit LDS-DMA launches (cn_conv_dgrad_w_mask) -- with the same bits in the gradient.  Everything else (a K split, bf16 storage,
+    the deterministic mode, F(4x4), and a residual on a layer conv_dgrad routes to F(2x2): conv_dgrad_res keeps that layer on
+    Winograd with an add pass, so cn_conv_dgrad_w_mask is not asked there either -- the ResNet trunk has no such layer, its
+    residuals ride on 1x1 launches) runs the data gradient and the pass: conv_dgrad / conv_dgrad_res, then act_bwd or
+    act_bwd_partials + sum_rows_into(defer=defer)."""
+    assert len(sums) <= 2
+    fused = None
+    if (MASK_EPILOGUE and not DETERMINISTIC and ACT_DTYPE == torch.float32 and gy.dtype == torch.float32 and mask.dtype == torch.float32
+            and (res is None or res.dtype == torch.float32) and DGRAD_FROM_W and not g.up and not _bf16_conv_ok(g)
+            and not _wino4_ok(g, g.cout, g.cin)):
+        gu = torch.empty(geom_in_shape(g, upsampled=True), device=gy.device, dtype=torch.float32)
+        assert tuple(gu.shape) == tuple(mask.shape), "conv_dgrad_mask: the mask has the shape of the data gradient"
+        s0 = _fptr(sums[0]) if len(sums) > 0 else None
+        s1 = _fptr(sums[1]) if len(sums) > 1 else None
+        if _wino_ok(g, g.cout, g.cin):
+            if res is None:
+                rc = lib.cn_conv_fwd_wino_ep(g.n, g.in_h, g.in_w, g.cout, g.cin, _ptr(_c(gy)), _ptr(_wino_filter(w, True)), _ptr(gu),
+                                             _ptr(_c(mask)), s0, s1, _stream())
+                fused = "wino"
+            else:
+                rc = CN_EUNSUPPORTED
+        else:
+            rc = lib.cn_conv_dgrad_w_mask(ctypes.byref(g), _ptr(_c(gy)), _fptr(_c(w)), None if res is None else _ptr(_c(res)),
+                                          _ptr(_c(mask)), _ptr(gu), s0, s1, _stream())
+            fused = "fwd2"
+        if rc == 0:
+            _log_mask(mask, ACT_RELU)
+            if sums and _SINK is not None:
+                _SINK.note_stream()                  # (the sums are added on this stream: the join orders itself behind it)
+            if fused == "wino":
+                prof_note_saved(wino_saved_flops(g))
+            if MASK_LOG is not None:
+                MASK_LOG.append(fused)
+            return gu
+        if rc != CN_EUNSUPPORTED:
+            check(rc, "cn_conv_fwd_wino_ep" if fused == "wino" else "cn_conv_dgrad_w_mask")
+        del gu
+    if MASK_LOG is not None:
+        MASK_LOG.append("pass")
+    gu = conv_dgrad(gy, w, g) if res is None else conv_dgrad_res(gy, w, g, res)
+    if not sums:
+        return act_bwd(gu, mask, ACT_RELU)
+    gu, part = act_bwd_partials(gu, mask, ACT_RELU)
+    for dst in sums:
+        sum_rows_into(part, dst, defer=defer)
+    return gu
+
+
 DGRAD_FROM_W = True
 MIXED_FIRST_LAYERS = True      # bf16 path: first-layer kernels that read / write both storage types
 WGRAD_WRITE, WGRAD_ADD, WGRAD_ZEROED = 0, 1, 2      # include/confignet_hip.h: CN_WGRAD_*

@@ -104,6 +104,17 @@ int cn_conv_dgrad_w(const CnConvGeom* g, const float* gy, const float* w, float*
 /* cn_conv_dgrad_w + res (res shaped like gu) in the launch's epilogue: the gradient of a tensor that feeds a convolution and a
  * skip connection (keras ResNet50's Add, real_encoder.py:13).  Stride-1, unsplit implicit-GEMM launches; else CN_EUNSUPPORTED. */
 int cn_conv_dgrad_w_res(const CnConvGeom* g, const float* gy, const float* w, const float* res, float* gu, void* stream);
+/* cn_conv_dgrad_w (res = NULL) / cn_conv_dgrad_w_res with the ReLU backward of the layer in front in the launch's epilogue:
+ *     gu = (data gradient (+ res)) * (mask > 0),  mask = that layer's saved ReLU output, shaped like gu
+ * -- bit for bit what the data-gradient call followed by cn_act_bwd(gu, mask, CN_ACT_RELU) stores -- and, where colsum / colsum2 are
+ * not NULL, colsum[c] += sum over all rows of gu[., c] (and the same into colsum2): the shift sums cn_act_bwd_bias takes in a pass of
+ * its own (real_encoder.py:13: a bottleneck's shortcut convolution receives the sums of its last convolution).  The destinations
+ * are added to with fp32 atomics, one add per column and workgroup; they are complete when the launch is.  Served by the unsplit
+ * fp32 launches of the LDS-DMA loop on 32-wide blocks, stride 1, no upsampling; CN_EUNSUPPORTED (nothing launched) for everything
+ * else (a K split, the implicit-GEMM loop, 48 output channels) and for any request with sums in deterministic mode: the caller
+ * then runs cn_conv_dgrad_w[_res] and cn_act_bwd[_bias]. */
+int cn_conv_dgrad_w_mask(const CnConvGeom* g, const float* gy, const float* w, const float* res, const float* mask, float* gu,
+                         float* colsum, float* colsum2, void* stream);
 /* Filter gradient (Conv*DBackpropFilter): gw[(t,ci),co] (+)= sum_m x[src(m,t),ci]*gy[m,co]; gw is overwritten,
  * or accumulated into when `accumulate` != 0 (the caller guarantees its previous content, e.g. zeros). */
 int cn_conv_wgrad(const CnConvGeom* g, const float* x, const float* gy, float* gw, int accumulate, void* stream);
@@ -247,6 +258,13 @@ int cn_conv_wgrad_thin(const CnConvGeom* g, const float* x, const float* gy, flo
 int cn_conv_wino_filter(const float* w, float* u, int cin, int cout, int dgrad, void* stream);
 int cn_conv_fwd_wino(int n, int h, int w, int cin, int cout, const float* x, const float* u, const float* bias, float* y,
                      int act, float slope, void* stream);
+/* The F(2x2) data-gradient launch (u made with dgrad = 1; no bias, no activation) with the ReLU backward of the layer in front in its
+ * output loop: y = conv * (mask > 0), mask = that layer's saved ReLU output shaped like y -- bit for bit cn_conv_fwd_wino followed by
+ * cn_act_bwd(y, mask, CN_ACT_RELU) -- and colsum[c] / colsum2[c] += the sums of y over all pixels (either may be NULL; fp32 atomics, one
+ * add per column and workgroup, complete when the launch is).  CN_EUNSUPPORTED (nothing launched) as cn_conv_fwd_wino, and for a
+ * request with sums in deterministic mode. */
+int cn_conv_fwd_wino_ep(int n, int h, int w, int cin, int cout, const float* x, const float* u, float* y, const float* mask,
+                        float* colsum, float* colsum2, void* stream);
 /* The same convolutions as Winograd F(4x4, 3x3) (csrc/winograd4.hip): 36 GEMMs per 4x4 output tile, 2.25 MFMA products per
  * output pixel and (ci, co) instead of 4.  u from cn_conv_wino4_filter ([36][cin][cout]; dgrad != 0: the flipped,
  * channel-swapped filter of the data gradient).  cn_conv_fwd_wino4 returns CN_EUNSUPPORTED (nothing launched) unless
@@ -277,6 +295,10 @@ int cn_conv_tune(int cfg, int splits, long wg_blocks);
  * 6 / 7 3x3 / 7x7-stride-2 first layer, 8 LDS-DMA loop, 9 implicit-GEMM loop, 10 nothing is launched.  Returns what the call would
  * return before launching: CN_OK, or the code (CN_EUNSUPPORTED / CN_EINVAL) of a request that launches nothing. */
 int cn_conv_fwd_plan(const CnConvGeom* g, int bt, int has_bias, int act, int has_res, int stats_mode, int x_dt, int y_dt, int out[8]);
+/* The same for a request with the mask epilogue (cn_conv_dgrad_w_mask: bt = 1, has_mask = 1, g = the data-gradient geometry): planned as
+ * a request with a residual that only the LDS-DMA loop serves.  has_mask = 0: cn_conv_fwd_plan. */
+int cn_conv_fwd_plan_ep(const CnConvGeom* g, int bt, int has_bias, int act, int has_res, int stats_mode, int has_mask, int x_dt, int y_dt,
+                        int out[8]);
 /* Tuning hook of the forward / data-gradient main loop (csrc/fwd2.hip, the LDS-DMA loop): loop = 1 / 0 forces it on / off for the
  * layers it can take, -1 = the built-in choice; kb = 16 / 32 its stage depth (0 = default), ns = 3 / 4 its stage count (0 = default),
  * np = 0 / 1 / 2 its loader waves (waves that only issue the LDS-DMA; -1 = default). */
