@@ -110,8 +110,8 @@ void cn_wgrad2_grouped(int cfg, const Wg2Jobs& J, unsigned grid, hipStream_t s);
 void cn_igemm_wgrad(int cfg, const CnConvGeom& g, const float* x, const float* gy, float* gw, int rows, float* parts, int tx, int ty,
                     int splits, dim3 grid, hipStream_t s);
 int cn_tiny_wgrad(const CnConvGeom& g, const float* x, const float* gy, float* gw, int blocks, float* parts, hipStream_t s);
-void cn_bf16_wgrad(int cfg, const CnConvGeom& g, const void* x, const void* gy, float* gw, int rows, int tx, int ty, int splits, dim3 grid,
-                   hipStream_t s);
+void cn_bf16_wgrad(int cfg, const CnConvGeom& g, const void* x, const void* gy, float* gw, int rows, float* parts, int tx, int ty, int splits,
+                   dim3 grid, hipStream_t s);
 int cn_c3_wgrad(const CnConvGeom& g, const float* x, const void* gy, int gy_dt, float* scratch, int tiles_x, int ntiles, int nparts,
                 size_t lds, hipStream_t s);
 void cn_c3_wgrad_reduce(const float* scratch, float* gw, int nparts, int count, int accumulate, hipStream_t s);

@@ -485,7 +485,7 @@ struct WgradPlan {
     int grid[3] = {0, 0, 0};
     size_t lds = 0;                  // C3 / THIN: dynamic LDS bytes
     size_t ws_floats = 0;            // workspace the caller provides: slabs (WGRAD2), partial filters (C3, THIN)
-    size_t det_floats = 0;           // TINY / IGEMM in deterministic mode: partials in the stream's workspace instead of atomics
+    size_t det_floats = 0;           // TINY / IGEMM / BF16 in deterministic mode: partials in the stream's workspace instead of atomics
     bool zero = false;               // the atomic routes: a zero pass precedes the launch when the target is to be written
     int sum = WG_SUM_NONE;
 };
@@ -538,7 +538,11 @@ bool igemm_wgrad_slices(const CnConvGeom& g, WgTile t, long wg_target, bool det,
 // than ~512 rows is mostly prologue + the tile's atomic adds; (2) one workgroup more than the CUs hold at once costs a whole extra
 // round -- the kernels hold 3 (128 x 128), 4 (128 x 96) or 5 workgroups per CU -- and the narrow tiles like two rounds; (3) with the
 // XCD order a slice count that is not a multiple of 8 leaves XCDs with one slice more than others.
-void bf16_wgrad_slices(const CnConvGeom& g, WgTile t, WgradPlan& p) {
+// det: the slices' partial filters go to the stream's deterministic workspace, so no more slices than it holds -- a clamp that the
+// rule above never reaches today (its largest slices x filter over taps 1..64, channels 8..2048 and 2^8..2^22 rows is 0.75 of the
+// workspace: tests/test_bf16_det_plan_cpu.py) and that only keeps a later rule from overflowing.  Where not even one partial filter
+// fits, one slice: it needs no partials.
+void bf16_wgrad_slices(const CnConvGeom& g, WgTile t, bool det, WgradPlan& p) {
     constexpr long KS = 32, min_rows = 512;          // (KS: bf16 reduction rows per LDS stage, igemm_bf16.hip)
     const long M = (long)g.n * g.out_d * g.out_h * g.out_w;
     const long Ktot = (long)g.k_d * g.k_h * g.k_w * g.cin;
@@ -556,6 +560,11 @@ void bf16_wgrad_slices(const CnConvGeom& g, WgTile t, WgradPlan& p) {
     rows = (rows + KS - 1) / KS * KS;
     p.rows = rows;
     p.splits = (M + rows - 1) / rows;
+    const long cap = std::max<long>(1, (long)(CN_DET_WS_FLOATS / ((size_t)Ktot * g.cout)));
+    if (det && p.splits > cap) {
+        p.rows = ((M + cap - 1) / cap + KS - 1) / KS * KS;
+        p.splits = (M + p.rows - 1) / p.rows;
+    }
 }
 
 // Pure: reads the geometry, the request (deterministic mode is part of it), cn_cu_count() and the tuning overrides.  The routes are asked in the order the
@@ -606,13 +615,17 @@ WgradPlan plan_conv_wgrad(const CnConvGeom& g, const WgradReq& q) {
             return p;
         }
     }
-    if (x16 && y16) {        // bf16 operands: 16-byte pieces of 8 channels, fp32 atomics on the tile in every mode
+    if (x16 && y16) {        // bf16 operands: 16-byte pieces of 8 channels; the slices' tiles meet in fp32 atomics, in deterministic mode in ordered slabs
         if (!may(CN_WG_BF16) || g.cin % 8 || g.cout % 8) return p;
         take(CN_WG_BF16, CN_FAM_BF16_WGRAD);
         p.cfg = wgrad_tile_cfg(g);
-        bf16_wgrad_slices(g, wgrad_tile(p.cfg), p);
+        bf16_wgrad_slices(g, wgrad_tile(p.cfg), q.det, p);
         sliced_grid(g, wgrad_tile(p.cfg), p);
         p.zero = true;
+        if (q.det && p.splits > 1) {      // (one slice: one writer per element and launch, the atomics are ordered as they are)
+            p.det_floats = (size_t)p.splits * count;
+            p.sum = WG_SUM_PARTS;
+        }
         return p;
     }
     if (!x32 || !y32) return p;
@@ -725,7 +738,7 @@ int run_conv_wgrad(const WgradPlan& p, const CnConvGeom& g, const WgradReq& q, c
             cn_igemm_wgrad(p.cfg, g, (const float*)x, (const float*)gy, gw, (int)p.rows, det, p.tx, p.ty, (int)p.splits, grid, s);
             break;
         default:
-            cn_bf16_wgrad(p.cfg, g, x, gy, gw, (int)p.rows, p.tx, p.ty, (int)p.splits, grid, s);
+            cn_bf16_wgrad(p.cfg, g, x, gy, gw, (int)p.rows, det, p.tx, p.ty, (int)p.splits, grid, s);
             break;
     }
     const bool sum_in_bracket = p.route != CN_WG_C3;      // (the K = 27 bracket has always closed in front of its reduction)

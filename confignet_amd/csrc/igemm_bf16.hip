@@ -220,7 +220,8 @@ __global__ __launch_bounds__(256) void igemm_bf16_kernel(CnConvGeom g, const bf1
 }
 
 // ---------------------------------------------------------------------------------------------
-// filter gradient:  GW[(t,ci), co] += sum_m X[src(m,t), ci] * GY[m, co]   (fp32 output, split over m, fp32 atomics)
+// filter gradient:  GW[(t,ci), co] += sum_m X[src(m,t), ci] * GY[m, co]   (fp32 output, split over m; the slices meet in fp32
+// atomics on GW or, in deterministic mode, in one slab per slice that cn_sum_parts adds in slice order)
 // ---------------------------------------------------------------------------------------------
 // Filter-gradient launches: (tap-channel tile, cout tile, row slice) of this workgroup.  tiles_x == 0: the 3-D grid as it is.  Else
 // the XCD-aware 1-D order (the fp32 kernels' rule, igemm_conv.hip: igemm_wgrad_kernel): workgroup id runs on XCD id % 8, and every tile of ONE row
@@ -238,10 +239,12 @@ __device__ __forceinline__ bool wgrad_tile_of_workgroup(int tiles_x, int tiles_y
     return true;
 }
 
-template <int WM, int WN, int TM, int TN>
+// SLABS: the deterministic mode's epilogue, an instance of its own -- the default mode's instruction stream is what it was without it
+template <int WM, int WN, int TM, int TN, bool SLABS>
 __global__ __launch_bounds__(256) void igemm_bf16_wgrad_tr_kernel(CnConvGeom g, const bf16_t* __restrict__ X,
                                                                const bf16_t* __restrict__ GY, float* __restrict__ GW,
-                                                               int rows_per_split, int tiles_x, int tiles_y, int nsplits) {
+                                                               float* __restrict__ parts, int rows_per_split, int tiles_x, int tiles_y,
+                                                               int nsplits) {
     static_assert(WM * WN == 4, "4 waves per workgroup");
     constexpr int BM = 32 * WM * TM, BN = 32 * WN * TN;
     constexpr int IPA = BM / 8, IPB = BN / 8;              // 8-channel pieces per position in each tile
@@ -408,7 +411,11 @@ __global__ __launch_bounds__(256) void igemm_bf16_wgrad_tr_kernel(CnConvGeom g, 
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = rbase + (r & 3) + 8 * (r >> 2);
-                if (row < Ktot) unsafeAtomicAdd(&GW[(long)row * g.cout + col], acc[i][j][r]);
+                if (row >= Ktot) continue;
+                // deterministic mode: this slice's partial filter goes to its own slab (plain stores, every element of the slab: the
+                // workspace is never cleared), the slabs are added in slice order
+                if constexpr (SLABS) parts[((long)bz * Ktot + row) * g.cout + col] = acc[i][j][r];
+                else unsafeAtomicAdd(&GW[(long)row * g.cout + col], acc[i][j][r]);
             }
         }
     }
@@ -486,12 +493,14 @@ extern "C" int cn_conv_dgrad_bf16(const CnConvGeom* gp, const uint16_t* gy, cons
     return conv_bf16(d, 1, gy, wd, nullptr, gu, CN_ACT_NONE, 0.f, (hipStream_t)stream);
 }
 
-// One launch of the bf16 filter gradient (fp32 atomics on the tile) on tile cfg with the slices, rows per slice and grid of the plan
-// (conv_dispatch.hip: bf16_wgrad_slices; tx / ty != 0: the XCD-ordered 1-D grid)
-void cn_bf16_wgrad(int cfg, const CnConvGeom& g, const void* x, const void* gy, float* gw, int rows, int tx, int ty, int splits, dim3 grid,
-                   hipStream_t s) {
-#define BW(WM, WN, TM, TN) hipLaunchKernelGGL((igemm_bf16_wgrad_tr_kernel<WM, WN, TM, TN>), grid, dim3(256), 0, s, g, (const bf16_t*)x, \
-                                              (const bf16_t*)gy, gw, rows, tx, ty, splits)
+// One launch of the bf16 filter gradient on tile cfg with the slices, rows per slice and grid of the plan (conv_dispatch.hip:
+// bf16_wgrad_slices; tx / ty != 0: the XCD-ordered 1-D grid).  parts == NULL: fp32 atomics of every slice's tile on gw.  Else
+// (deterministic mode) slice z writes its tile to parts[z][Ktot][cout] and gw is not touched: the caller adds the slabs.
+void cn_bf16_wgrad(int cfg, const CnConvGeom& g, const void* x, const void* gy, float* gw, int rows, float* parts, int tx, int ty, int splits,
+                   dim3 grid, hipStream_t s) {
+#define BW1(WM, WN, TM, TN, SLABS) hipLaunchKernelGGL((igemm_bf16_wgrad_tr_kernel<WM, WN, TM, TN, SLABS>), grid, dim3(256), 0, s, g, \
+                                                      (const bf16_t*)x, (const bf16_t*)gy, gw, parts, rows, tx, ty, splits)
+#define BW(WM, WN, TM, TN) do { if (parts) BW1(WM, WN, TM, TN, true); else BW1(WM, WN, TM, TN, false); } while (0)
     switch (cfg) {
         case 3: BW(4, 1, 1, 1); break;       // 128 (tap,ci) x 32 co
         case 4: BW(4, 1, 1, 3); break;       // 128 x 96
@@ -499,4 +508,5 @@ void cn_bf16_wgrad(int cfg, const CnConvGeom& g, const void* x, const void* gy, 
         default: BW(2, 2, 1, 1); break;      // 64 x 64
     }
 #undef BW
+#undef BW1
 }

@@ -34,7 +34,8 @@ def _stream():
 
 
 # Deterministic mode (CN_DETERMINISTIC=1 or set_deterministic(True); include/confignet_hip.h: cn_set_deterministic): every
-# reduction of the fp32 path in a fixed order instead of fp32 atomics -- two runs on the same inputs are bit-identical.  Also
+# reduction in a fixed order instead of fp32 atomics, in fp32 and in bf16 storage (set_activation_dtype: the bf16 filter gradient
+# adds its row slices' slabs in slice order) -- two runs on the same inputs are bit-identical.  Also
 # switches off what reorders ADDS between streams: the generator step's fork (both branches add into the generator's slots).
 DETERMINISTIC = False
 

@@ -353,13 +353,16 @@ int cn_gemm(int trans_a, int trans_b, int m, int n, int k, const float* a, int l
 int cn_gemm_plan(int trans_a, int trans_b, int m, int n, int k, int ldc, int has_bias, int act, int accumulate, int deterministic,
                  int out[9]);
 
-/* Deterministic mode (process-wide; switch between steps, not inside a captured graph): with on != 0 every reduction of the
- * fp32 path runs in a fixed order -- statistics passes, split-K of cn_conv_fwd / cn_gemm, filter gradients and loss reductions
+/* Deterministic mode (process-wide; switch between steps, not inside a captured graph): with on != 0 every reduction
+ * runs in a fixed order -- statistics passes, split-K of cn_conv_fwd / cn_gemm, filter gradients and loss reductions
  * through per-split partials that a second launch adds in index order, the rotation's scatter by one wave per (sample, 8
  * channels) in voxel order -- so two runs on the same inputs give bit-identical results (at a cost: see DESIGN.md).  Allocates 16 per-stream
  * workspaces of 64 MiB on first use; a workspace handed out while its stream was being captured stays bound to that stream
  * (a replayed graph holds the pointer) until cn_det_release_stream(stream), and a launch that finds every workspace bound that
- * way fails with CN_E* instead of sharing scratch.  The bf16 family is not covered. */
+ * way fails with CN_E* instead of sharing scratch.  The bf16 family is covered: its forward and data gradient have no split, and
+ * its filter gradient (cn_conv_wgrad_bf16, cn_conv_wgrad_dt on bf16 operands) writes one slab per row slice into the stream's
+ * workspace and adds the slabs in slice order instead of adding every slice's tile with fp32 atomics -- the same route, tile,
+ * slices and grid as in the default mode; cn_conv_wgrad_plan reports the sum in out[10]. */
 int cn_set_deterministic(int on);
 int cn_get_deterministic(void);
 /* The caller has destroyed every graph captured on `stream` (or the stream itself): its workspace may be re-bound. */
