@@ -63,7 +63,12 @@ def conv_adain(x, z, w6, spec, sb=None):
         sb = F.linear(F.linear(z, m0, b0, ACT_LRELU, TF_LRELU), m1, b1)
     with ops.request_stats("act"):                   # AdaIn's statistics from the convolution's epilogue where the launch carries them
         x = F.conv(x, ck, cb, spec, ACT_LRELU, KERAS_LRELU)
-    return F.adain(x, sb)
+    if ops.STORED_LOG is not None:
+        ops._log_stored(x)                                        # (test instrument: ops.stored_log, here and below)
+    x = F.adain(x, sb)
+    if ops.STORED_LOG is not None:
+        ops._log_stored(x)
+    return x
 
 
 DISCR_CONV = ConvSpec((3, 3), stride=2)
@@ -81,11 +86,17 @@ def discr_block(x, w4, return_styles, twice_differentiable=False, intermediates=
     else:
         with ops.request_stats("pre4", KERAS_LRELU):     # the tail's four sums from the convolution's epilogue where the launch carries them
             x = F.conv(x, ck, cb, DISCR_CONV)
+    if ops.STORED_LOG is not None:
+        ops._log_stored(x)
     if not twice_differentiable:
         y, style, mean, q, smean, ssd = F.DiscrTailFn.apply(x, gamma, beta, return_styles, KERAS_LRELU)
+        if ops.STORED_LOG is not None:
+            ops._log_stored(y)
         if intermediates is not None:
             intermediates.append({"x": x, "mean": mean, "q": q, "smean": smean, "ssd": ssd, "in_shape": in_shape})
         return y, style
     styles = F.layer_style(x) if return_styles else None
     x = F.instance_norm(F.lrelu(x, KERAS_LRELU), gamma, beta)
+    if ops.STORED_LOG is not None:
+        ops._log_stored(x)
     return x, styles

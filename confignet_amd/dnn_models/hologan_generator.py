@@ -3,6 +3,7 @@ import numpy as np
 import torch
 
 from .. import functional as F
+from .. import ops
 from ..nn import Net, glorot_uniform
 from ..ops import ACT_LRELU, ACT_TANH, ConvSpec
 from .building_blocks import KERAS_LRELU, TF_LRELU, conv_adain
@@ -82,6 +83,8 @@ class HologanGenerator(Net):
         # learned constant: zeros(N,1) @ kernel + bias (l.133-136)
         zeros = torch.zeros((n, 1), device=self.device, dtype=torch.float32)
         x = F.linear(zeros, w[0], w[1]).reshape(n, *self.const_shape)
+        if ops.STORED_LOG is not None:
+            ops._log_stored(x)                                    # (test instrument: ops.stored_log, here and below)
         zs = [inp["z_2d_0"], inp["z_2d_1"], inp["z_2d_2"], inp["z_2d_2"], inp["z_2d_2"]]
         sbs = [None] * (2 + self.n_2d)
         if self.mlp_bank and all(z.dtype == torch.float32 and z.dim() == 2 and z.shape[0] <= 32 for z in [inp["z_3d_0"], inp["z_3d_1"]] + zs):
@@ -93,11 +96,19 @@ class HologanGenerator(Net):
         x = conv_adain(x, inp["z_3d_0"], w[2:8], C3_UP, sbs[0])       # UpSampling3D folded (l.139-142)
         x = conv_adain(x, inp["z_3d_1"], w[8:14], C3_UP, sbs[1])      # l.143-144
         x = F.rotate3d(x, inp["rotation"])                            # l.147-148
+        if ops.STORED_LOG is not None:
+            ops._log_stored(x)
         x = F.conv(x, w[14], w[15], C3, ACT_LRELU, KERAS_LRELU)       # map_3d_post (l.49-54,151)
+        if ops.STORED_LOG is not None:
+            ops._log_stored(x)
         x = F.conv(x, w[16], w[17], C3, ACT_LRELU, KERAS_LRELU)
+        if ops.STORED_LOG is not None:
+            ops._log_stored(x)
         s = x.shape
         x = x.reshape(s[0], s[1], s[2], s[3] * s[4])                  # depth collapse (l.153-156)
         x = F.conv(x, w[18], w[19], C1, ACT_LRELU, TF_LRELU)          # projection_conv (l.56,157)
+        if ops.STORED_LOG is not None:
+            ops._log_stored(x)
         i = 20
         for j in range(self.n_2d):
             x = conv_adain(x, zs[j], w[i:i + 6], C4 if j == 0 else C4_UP, sbs[2 + j])   # UpSampling2D folded (l.159-170)

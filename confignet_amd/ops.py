@@ -1319,6 +1319,33 @@ def _log_mask(t, act=None):
         BRANCH_LOG.append(("act", (t.detach().float() > 0).reshape(-1).cpu()))
 
 
+# ---------------------------------------------------------------------------------------------
+# Test instrument (tests/test_bf16_grads_gpu.py: bf16 network gradients at the product's own forward state): with `stored_log()`
+# active the generator, the discriminator / latent regressor and their blocks append every activation tensor they hand from one
+# kernel to the next -- the points oracle.ref_nets marks with `O.stored(...)`, in forward order -- as a host copy of the value as
+# it is STORED (a tensor that is still fp32 at its site and converted by the consuming convolution, the generator's learned
+# constant, is logged in the activation type).  The oracle then REPLAYS these values (oracle.ref_ops.StoredReplay), so both
+# gradients are taken at one forward state.  Off (None) in the product path: one `is not None` test per site.
+# ---------------------------------------------------------------------------------------------
+STORED_LOG = None
+
+
+class stored_log:
+    def __enter__(self):
+        global STORED_LOG
+        STORED_LOG = self.log = []
+        return self.log
+
+    def __exit__(self, *exc):
+        global STORED_LOG
+        STORED_LOG = None
+
+
+def _log_stored(t):
+    if STORED_LOG is not None:
+        STORED_LOG.append(t.detach().to(_act_out_dtype(t.shape[-1])).float().cpu())
+
+
 def act_fwd(x, act, slope=0.0):
     y = torch.empty_like(x)
     check(lib.cn_act_fwd(_ptr(x), _ptr(y), x.numel(), act, slope, _dt(x), _stream()), "cn_act_fwd")

@@ -41,14 +41,13 @@ def generator_forward(w, z, rotation, res, return_intermediates=False):
     # learned_input: Dense(32768, kernel zeros-init, bias ones-init) on zeros(N,1) (l.24-27,133-136)
     k, b = c.take(2)
     x = O.stored(O.dense(torch.zeros(n, 1, dtype=z30.dtype), k, b).reshape(n, 4, 4, 4, 512))
-    x = O.upsample2(x)                                                   # l.139
-    # map_3d_0 / map_3d_1: Conv3D k3 same -> LeakyReLU(0.3) -> AdaIn (building_blocks.py:37-44)
+    # UpSampling3D (l.139) + map_3d_0 / map_3d_1: Conv3D k3 same -> LeakyReLU(0.3) -> AdaIn (building_blocks.py:37-44)
+    # (O.up_conv_same(x, ...) == O.conv_same(O.upsample2(x), ...); O.stored: identity outside O.bf16_storage)
     ck, cb, *mlp = c.take(6)
-    x = O.stored(O.adain(O.stored(O.leaky_relu(O.conv_same(x, ck, cb), 0.3)), z30, mlp, 0.2))     # (O.stored: identity outside O.bf16_storage)
+    x = O.stored(O.adain(O.stored(O.leaky_relu(O.up_conv_same(x, ck, cb), 0.3)), z30, mlp, 0.2))
     inter["a3d0"] = x
-    x = O.upsample2(x)                                                   # l.143
-    ck, cb, *mlp = c.take(6)
-    x = O.stored(O.adain(O.stored(O.leaky_relu(O.conv_same(x, ck, cb), 0.3)), z31, mlp, 0.2))
+    ck, cb, *mlp = c.take(6)                                             # UpSampling3D (l.143)
+    x = O.stored(O.adain(O.stored(O.leaky_relu(O.up_conv_same(x, ck, cb), 0.3)), z31, mlp, 0.2))
     inter["a3d1"] = x
     # rotation (l.147-148)
     x = O.stored(O.transform_3d_grid(x, O.euler_angles_to_matrix(rotation)))
@@ -70,14 +69,13 @@ def generator_forward(w, z, rotation, res, return_intermediates=False):
         zs.append(z22)
     if res > 256:
         zs.append(z22)
-    for i, zz in enumerate(zs):                                          # l.159-170
-        ck, cb, *mlp = c.take(6)
-        x = O.stored(O.leaky_relu(O.conv_same(x, ck, cb), 0.3))
+    for i, zz in enumerate(zs):                                          # l.159-170: every block ends in UpSampling2D, which
+        ck, cb, *mlp = c.take(6)                                         # is evaluated with the convolution that reads it
+        x = O.stored(O.leaky_relu((O.up_conv_same if i else O.conv_same)(x, ck, cb), 0.3))
         x = O.stored(O.adain(x, zz, mlp, 0.2))
         inter["a2d%d" % i] = x
-        x = O.upsample2(x)
     ck, cb = c.take(2)
-    x = torch.tanh(O.conv_same(x, ck, cb))                               # map_final (l.101,172)
+    x = torch.tanh(O.up_conv_same(x, ck, cb))                            # map_final (l.101,172)
     c.done()
     if return_intermediates:
         return x, inter

@@ -40,31 +40,169 @@ def _to_cl(x):   # channels-first -> channels-last
 # accumulation, the rounding of pre-summed class filters and values that sit on a bf16 rounding boundary.
 # ----------------------------------------------------------------------------
 _BF16_STORAGE = False
+_ROUND_GRADS = False     # bf16_storage(round_grads=True): every storage point also rounds the gradient that flows back through it
+_ONLY_POINT = None       # bf16_storage(only_point=j): of the `stored` calls the j-th alone rounds (attribution runs)
+_ROUND_FILTERS = True
+_CLASS_FILTERS = False   # bf16_storage(class_filters=True): UpSampling + Conv layers round their PRE-SUMMED class filters (up_conv_same)
+_STORED_CALLS = 0
 
 
 class bf16_storage:
+    """round_grads: every storage point is also a storage point of the BACKWARD pass -- the gradient flowing back through it is
+    rounded to bf16 (differentiably, so the inner gradient of an R1 term is rounded too): the size of what bf16 storage of
+    gradients can cost, the yardstick of tests/test_bf16_grads_gpu.py.  only_point=j / filters=False: the attribution runs of
+    tests/test_bf16_grad_yardstick_cpu.py (one storage point at a time with exact filters; only_point=-1: the filters alone).
+    class_filters: the collapsed product (confignet_amd.ops.UPFOLD) -- an UpSampling + Conv layer runs per output-parity class on
+    filters pre-summed in fp32 and rounded to bf16 ONCE (up_conv_same) instead of on the bf16 roundings of its single taps."""
+
+    def __init__(self, round_grads=False, only_point=None, filters=True, class_filters=False):
+        self.cfg = (True, round_grads, only_point, filters, class_filters)
+
     def __enter__(self):
-        global _BF16_STORAGE
-        self.prev, _BF16_STORAGE = _BF16_STORAGE, True
+        global _BF16_STORAGE, _ROUND_GRADS, _ONLY_POINT, _ROUND_FILTERS, _CLASS_FILTERS, _STORED_CALLS
+        self.prev = (_BF16_STORAGE, _ROUND_GRADS, _ONLY_POINT, _ROUND_FILTERS, _CLASS_FILTERS)
+        _BF16_STORAGE, _ROUND_GRADS, _ONLY_POINT, _ROUND_FILTERS, _CLASS_FILTERS = self.cfg
+        _STORED_CALLS = 0
 
     def __exit__(self, *exc):
-        global _BF16_STORAGE
-        _BF16_STORAGE = self.prev
+        global _BF16_STORAGE, _ROUND_GRADS, _ONLY_POINT, _ROUND_FILTERS, _CLASS_FILTERS
+        _BF16_STORAGE, _ROUND_GRADS, _ONLY_POINT, _ROUND_FILTERS, _CLASS_FILTERS = self.prev
 
 
 def _bf16_round(t):
     return (t.detach().to(torch.float32).to(torch.bfloat16).to(t.dtype) - t.detach()) + t      # (straight-through for autograd)
 
 
+class _RoundGradFn(torch.autograd.Function):
+    """Identity whose backward rounds the gradient to bf16 (straight-through, so it can be differentiated again)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _bf16_round(g)
+
+
+class StoredReplay:
+    """Test instrument, not part of the restated algorithm (as BranchControl).  `log` = the tensors the PRODUCT stored at the
+    points that correspond to `stored` (confignet_amd.ops.stored_log: host copies, forward order).  With a replay active,
+    `stored(x)` inside bf16_storage() returns the product's value for this call, with the identity as derivative like
+    _bf16_round: the oracle's gradient is then taken at the product's own forward state.  Matching is by order among the logged
+    entries of the call's shape; where the product ran several of this oracle's calls as one stacked batch (or the other way
+    round: the real and the fake batch of compute_discriminator_loss), the sample blocks are matched in order.  `report()`
+    lists per call the shape, the share of elements whose logged value differs from this oracle's own bf16 rounding of x, and
+    the relative L2 of that difference, and what found no match on either side.  `recording` (a list) receives what every
+    `stored` call returned, in order: one oracle pass's own storage state in the format of `log`."""
+    active = False
+    recording = None
+    entries = {}         # shape -> [{"t": tensor, "used": sample blocks taken so far, "blocks": k (1 unless split)}]
+    counts = {}          # shape -> calls of that shape so far
+    calls = []
+    unmatched = []
+
+    @classmethod
+    def start(cls, log=None, recording=None):
+        cls.active, cls.entries, cls.counts, cls.calls, cls.unmatched = log is not None, {}, {}, [], []
+        cls.recording = recording
+        for t in log or ():
+            t = t.detach().to(torch.float64)
+            cls.entries.setdefault(tuple(t.shape), []).append({"t": t, "used": 0})
+
+    @classmethod
+    def stop(cls):
+        cls.active, cls.recording = False, None
+
+    @classmethod
+    def report(cls):
+        """{"calls": [{"call", "shape", "share", "rel"}], "unmatched": [calls that a gradient reached without a logged entry],
+        "leftover": [shapes of logged entries (or sample blocks of them) that no call took]}."""
+        left = []
+        for shape, es in cls.entries.items():
+            for e in es:
+                if e["used"] < e.get("blocks", 1):
+                    left.append({"shape": shape, "blocks_used": e["used"], "blocks": e.get("blocks", 1)})
+        return {"calls": list(cls.calls), "unmatched": [u for u in cls.unmatched if u["reached"][0]], "leftover": left}
+
+    @classmethod
+    def _find(cls, shape):
+        j = cls.counts.get(shape, 0)
+        cls.counts[shape] = j + 1
+        es = cls.entries.get(shape)
+        if es:                                           # the same launch on both sides: the j-th entry of this shape
+            if j < len(es) and not es[j]["used"]:
+                es[j]["used"] = 1
+                return es[j]["t"]
+            return None
+        n, rest = shape[0], shape[1:]
+        # the product ran k of this oracle's calls as ONE stacked batch: the sample blocks of the logged tensors, block by block
+        # (this oracle runs one sub-batch through the whole network, then the next)
+        for s2, es in cls.entries.items():
+            if s2[1:] == rest and s2[0] > n and s2[0] % n == 0:
+                k = s2[0] // n
+                for b in range(k):
+                    for e in es:
+                        e["blocks"] = k
+                        if e["used"] == b:
+                            e["used"] = b + 1
+                            return e["t"][b * n:(b + 1) * n]
+                return None
+        # ... or this oracle call works on a stack whose k sample blocks the product ran as separate passes: with m = (logged
+        # entries) / k entries per pass, call j takes entry j of every pass
+        for s2, es in cls.entries.items():
+            if s2[1:] == rest and s2[0] < n and n % s2[0] == 0 and len(es) % (n // s2[0]) == 0:
+                k = n // s2[0]
+                m = len(es) // k
+                parts = [es[j + m * p] for p in range(k)] if j < m else []
+                if parts and not any(e["used"] for e in parts):
+                    for e in parts:
+                        e["used"] = 1
+                    return torch.cat([e["t"] for e in parts], dim=0)
+                return None
+        return None
+
+    @classmethod
+    def take(cls, x):
+        xd = x.detach()
+        shape = tuple(xd.shape)
+        logged = cls._find(shape)
+        cid = len(cls.calls) + len(cls.unmatched)
+        if logged is None:
+            reached = [False]
+            cls.unmatched.append({"call": cid, "shape": shape, "reached": reached})
+            if x.requires_grad:
+                def note(g, reached=reached):
+                    reached[0] = reached[0] or bool((g != 0).any())
+                x.register_hook(note)
+            else:
+                reached[0] = True                        # (a value-only pass: the forward state itself would be another one)
+            return _bf16_round(x)
+        own = xd.to(torch.float32).to(torch.bfloat16).to(xd.dtype)
+        diff = logged - own
+        cls.calls.append({"call": cid, "shape": shape, "share": float((diff != 0).double().mean()),
+                          "rel": float(diff.norm() / (own.norm() + 1e-300))})
+        return (logged.to(xd.dtype) - xd) + x
+
+
 def stored(x):
     """x as the product keeps it in HBM between two kernels (identity outside bf16_storage)."""
-    return _bf16_round(x) if (_BF16_STORAGE and x.shape[-1] > 4) else x
+    global _STORED_CALLS
+    if not (_BF16_STORAGE and x.shape[-1] > 4):
+        return x
+    j, _STORED_CALLS = _STORED_CALLS, _STORED_CALLS + 1
+    if _ONLY_POINT is not None and j != _ONLY_POINT:
+        return x
+    y = StoredReplay.take(x) if StoredReplay.active else _bf16_round(x)
+    if StoredReplay.recording is not None:
+        StoredReplay.recording.append(y.detach().clone())
+    return _RoundGradFn.apply(y) if (_ROUND_GRADS and y.requires_grad) else y
 
 
 def conv_same(x, w, b=None, stride=1):
     """keras.layers.Conv2D/Conv3D(padding="same") -- cross-correlation, asymmetric
     SAME padding (building_blocks.py:29,65,91; hologan_generator.py:50-56,101)."""
-    if _BF16_STORAGE and w.shape[-2] % 8 == 0 and w.shape[-1] % 8 == 0:
+    if _BF16_STORAGE and _ROUND_FILTERS and w.shape[-2] % 8 == 0 and w.shape[-1] % 8 == 0:
         w = _bf16_round(w)
     nd = x.dim() - 2
     ks = w.shape[:nd]
@@ -78,6 +216,63 @@ def conv_same(x, w, b=None, stride=1):
     fn = F.conv2d if nd == 2 else F.conv3d
     y = fn(xc, wc, b, stride=stride)
     return _to_cl(y)
+
+
+def _class_taps(extent, k):
+    """Along one axis of UpSampling(2) + conv(k, SAME): per output parity p, {source offset s: [taps kk]} -- output 2 m + p reads
+    the upsampled rows u = 2 m + p - P + kk, i.e. the stored rows m + floor((p - P + kk) / 2)."""
+    lo, _, _ = same_pad(2 * extent, k, 1)
+    out = []
+    for p in range(2):
+        groups = {}
+        for kk in range(k):
+            groups.setdefault((p - lo + kk) // 2, []).append(kk)
+        out.append(groups)
+    return out
+
+
+def up_conv_classes(x, w, b=None, round_bf16=False):
+    """conv_same(upsample2(x), w, b) evaluated per output-parity class on the stored grid: the taps that read one stored element
+    are pre-summed (an exact identity).  round_bf16: the class filters are summed in fp32, tap order ascending, and rounded to
+    bf16 once, as the product prepares them (csrc/upfold.hip); the derivative w.r.t. the taps stays that of the exact sum."""
+    import itertools
+    nd = x.dim() - 2
+    spatial = x.shape[1:1 + nd]
+    axes = [_class_taps(spatial[i], w.shape[i]) for i in range(nd)]
+    w32 = w.detach().to(torch.float32)
+    out = x.new_zeros((x.shape[0], *[2 * e for e in spatial], w.shape[-1]))
+    fn = F.conv2d if nd == 2 else F.conv3d
+    xc = _to_cf(x)
+    for parity in itertools.product(range(2), repeat=nd):
+        groups = [axes[i][parity[i]] for i in range(nd)]
+        offs = [sorted(g) for g in groups]
+        rows = []
+        for cell in itertools.product(*offs):
+            taps = list(itertools.product(*[groups[i][cell[i]] for i in range(nd)]))
+            wc = sum(w[t] for t in taps)
+            if round_bf16:
+                s32 = torch.zeros_like(w32[taps[0]])
+                for t in taps:
+                    s32 = s32 + w32[t]
+                wc = (s32.to(torch.bfloat16).to(w.dtype) - wc.detach()) + wc
+            rows.append(wc)
+        wc = torch.stack(rows).reshape(*[len(o) for o in offs], w.shape[-2], w.shape[-1])
+        pads = []
+        for i in reversed(range(nd)):
+            pads += [-offs[i][0], offs[i][-1]]
+        y = fn(F.pad(xc, pads), wc.permute(nd + 1, nd, *range(nd)), b)
+        out[(slice(None), *[slice(p, None, 2) for p in parity])] = _to_cl(y)
+    return out
+
+
+def up_conv_same(x, w, b=None):
+    """keras UpSampling2D/3D() + Conv(padding="same") (hologan_generator.py:139-170).  Inside bf16_storage(class_filters=True)
+    the layers the product collapses (confignet_amd.ops.upfold_ok on the bf16 matrix cores) run on rounded class filters."""
+    ks = tuple(w.shape[:-2])
+    if (_BF16_STORAGE and _CLASS_FILTERS and _ROUND_FILTERS and w.shape[-2] % 8 == 0 and w.shape[-1] % 8 == 0
+            and all(2 <= k <= 4 for k in ks) and math.prod(k + 1 if k >= 3 else 3 for k in ks) <= 64):
+        return up_conv_classes(x, w, b, round_bf16=True)
+    return conv_same(upsample2(x), w, b)
 
 
 def conv_valid_padded(x, w, b, stride, pad):
@@ -118,10 +313,13 @@ class BranchControl:
     forced = None        # {"act": {numel: [{"mask", "pop"}]}, "pool": {key: [fp32 input]}}
     force_margin = 2e-3  # a forced decision may differ from the oracle's own only where |x| < force_margin * mean|x|
     report = None
+    mask_log = None      # a list: receives ("act", mask) of every activation call, the decisions this pass TOOK (forced ones
+                         # included), in the format of `forced` -- one oracle pass's decisions can be forced into another
 
     @classmethod
-    def start(cls, record=False, flips=(), forced=None):
+    def start(cls, record=False, flips=(), forced=None, mask_log=None):
         cls.active, cls.record, cls.flips, cls.calls, cls.cand = True, record, frozenset(flips), 0, {}
+        cls.mask_log = mask_log
         cls.forced, cls.report = None, {"forced_calls": 0, "forced_decisions": 0, "max_margin": 0.0, "unmatched": []}
         if forced is not None:
             acts, pools = {}, {}
@@ -139,6 +337,7 @@ class BranchControl:
         cls.active = cls.record = False
         cls.flips = frozenset()
         cls.forced = None
+        cls.mask_log = None
 
     @classmethod
     def candidates(cls):
@@ -239,14 +438,20 @@ def _branch_act(x, neg):
     cid, bc.calls = bc.calls, bc.calls + 1
     if bc.forced is not None:
         if not x.requires_grad:
+            if bc.mask_log is not None:
+                bc.mask_log.append(("act", (xd > 0).reshape(-1)))
             return x * m
         pm, info = bc.forced_mask(xd)
+        if bc.mask_log is not None:
+            bc.mask_log.append(("act", ((xd > 0) if pm is None else pm).reshape(-1).clone()))
         if pm is None:
             y = x * m
             bc._unmatched(y, "activation", call=cid, shape=tuple(x.shape), **info)
             return y
         m = torch.where(pm.reshape(x.shape), torch.ones((), dtype=x.dtype), torch.full((), neg, dtype=x.dtype))
         return x * m
+    if bc.mask_log is not None and not bc.flips:
+        bc.mask_log.append(("act", (xd > 0).reshape(-1)))
     for c, i in bc.flips:
         if c == cid:
             mf = m.reshape(-1)

@@ -8,8 +8,10 @@ Tolerances are stated per test.  A bf16 value carries 8 significant bits (relati
     the fp32 filter gradient has no output rounding: 2e-4 of its scale, like the fp32 family;
   * whole networks / losses are compared with the fp32-exact oracle on the unrounded weights: every layer rounds its
     output once, so the error grows like sqrt(depth) * 2^-9 relative: 3e-2 of the output scale is asserted for the
-    generator image (relative L2; single pixels up to 0.2 of the tanh range) and the loss scalars
-    (scripts/dev/bf16_diag.py prints the layer-by-layer growth).
+    generator image (relative L2; single pixels up to 0.2 of the tanh range) and the loss scalars.  The GRADIENTS of whole
+    networks are held here at rel-L2 0.3 against the fp32 oracle, which is all a comparison across two forward states can give
+    (see the comment at those assertions); at the product's own forward state they are held to 4 * b_k + 5e-3, about 1 - 3 %,
+    in tests/test_bf16_grads_gpu.py.
 
 The sharp bf16 checks are elsewhere: the kernels bit for bit in tests/test_conv_edges_gpu.py (section 6), tests/test_wgrad_edges_gpu.py,
 tests/test_stream_edges_gpu.py, tests/test_nc_edges_gpu.py and tests/test_filter_prep_gpu.py; the normalisation tails in
@@ -219,8 +221,8 @@ def test_bf16_generator_and_discriminator_loss_against_the_fp32_oracle():
     assert img.dtype == torch.float32                                   # 3-channel images stay fp32
     wr = [t64(w) for w in g.get_weights()]
     ref = R.generator_forward(wr, t64(z), t64(rot), 128)
-    # 15 bf16-stored layers: the error grows by ~0.1-0.3 % relative L2 per layer (scripts/dev/bf16_diag.py prints it layer by
-    # layer: 0.28 % after the first Conv3D, 1.4 % at the image); single pixels of the tanh output deviate by up to ~0.1
+    # 15 bf16-stored layers: the error grows by ~0.1-0.3 % relative L2 per layer (0.28 % after the first Conv3D, 1.4 % at the
+    # image); single pixels of the tanh output deviate by up to ~0.1
     diff = img.detach().cpu().double() - ref
     rel, err = float(diff.norm() / ref.norm()), float(diff.abs().max())
     assert rel <= 3e-2 and err <= 0.2, "bf16 generator image: rel-L2 %.3e, max abs err %.3e (tanh output in [-1, 1])" % (rel, err)
@@ -255,10 +257,14 @@ def test_bf16_generator_and_discriminator_loss_against_the_fp32_oracle():
         if gr is None or float(gr.norm()) == 0.0:
             continue
         assert p.grad.dtype == torch.float32
-        # a pre-activation within the accumulated bf16 error of zero (~0.5 % of the elements per layer) takes the other LeakyReLU
-        # branch than in the oracle; each such flip changes a gradient entry by the factor 0.3 <-> 1, which adds ~5 % relative L2
-        # per activation layer in quadrature (14 % measured at the learned input, the deepest tensor).  The kernels themselves
-        # are pinned at 2^-8 by the raw-op test above.
+        # This is the statement against the fp32 oracle, and it cannot be sharp: the bf16 gradient is taken at ANOTHER FORWARD
+        # POINT -- every stored tensor is off by 2^-9, and the normalisation stacks amplify that (14 % measured at the learned
+        # input, the deepest tensor).  It is not the LeakyReLU branches: on the oracle alone (tests/test_bf16_grad_yardstick_cpu.py,
+        # profiles/bf16_grad_attribution.txt; 64 x 64 discriminator loss with R1, n = 2) the plain and the bf16-storage oracle
+        # differ by 0.070 - 0.074 with every decision held EQUAL and by 0.073 - 0.090 with the decisions free, 212 of 376 832
+        # decisions differ, and bf16 storage of the gradients themselves costs 2e-3 - 5e-3.  A backward kernel that is wrong by
+        # 10 % in one layer passes here; it does not pass tests/test_bf16_grads_gpu.py, which compares at the product's own
+        # forward state (stored tensors replayed, decisions forced) with a bound measured on the oracle, 1 - 3 %.
         got = p.grad.detach().cpu().double()
         rel = float((got - gr).norm() / gr.norm())
         cos = float((got * gr).sum() / (got.norm() * gr.norm()))
@@ -301,7 +307,8 @@ def test_bf16_generator_and_discriminator_loss_against_the_fp32_oracle():
         assert rel <= 0.3 and cos >= 0.95, "bf16 discriminator (R1) grad[%d] %s: rel-L2 %.3e cos %.4f" % (i, tuple(p.shape), rel, cos)
     got = torch.cat([p.grad.detach().cpu().double().reshape(-1) for p in d.weights])
     ref = torch.cat([r.reshape(-1) for r in gr])
-    # measured: rel-L2 0.24, cos 0.972 (run-to-run +-0.002: atomics order); the branch flips above, through two passes
+    # measured: rel-L2 0.24, cos 0.972 (run-to-run +-0.002: atomics order): the other forward point above, under the R1 term's
+    # instance-norm stack (single storage points of the 4 x 4 block move these gradients by 0.14, profiles/bf16_grad_attribution.txt)
     assert float((got - ref).norm() / ref.norm()) <= 0.3 and float((got * ref).sum() / (got.norm() * ref.norm())) >= 0.96
 
 
